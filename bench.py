@@ -1,8 +1,16 @@
 """Benchmark: body-steps/s of the rigid-body hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dtype f64]
-                    [--scaling strong|weak]
+                    [--scaling strong|weak] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...      (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+`--full` adds what the headline figure does not need: `cpu_baseline` and
+`accuracy` (one GPU), the per-launch kernel timing run (several GPUs).
+`--dump-outputs DIR` writes the state after the last timed step, as a caller
+of the timed path reads it (gather_state), to DIR/qpos.npy (n, 7) and
+DIR/qvel.npy (n, 6) in the world's precision; the scenes are seeded, so the
+same arguments give the same inputs on every run.
 
 Workload: C3 (BASELINE.json configs[2]) in fp64 — 65,536 spheres r 0.1 on
 flat ground, e 0.8, mu 0.3, dt 0.01, seeded synthetic initial conditions
@@ -44,14 +52,14 @@ roofline: algorithmic HBM bytes of the step kernel (248 B per
 sphere body-step in fp64) x owned bodies / its average launch duration.
 One rank: HIP events recorded on the world's stream (torch's current
 stream) around the timed region, which is exactly K graph-replayed
-step-kernel launches, / K.  Several ranks: an event pair around each
+step-kernel launches, / K.  Several ranks (--full): an event pair around each
 step-kernel launch over a second run of K steps.  `traffic` /
 `traffic_lower`: the PMC bounds per launch from the committed
 profiles/pmc_traffic.json (rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this
 command, profiles/collect_pmc.py), named in `traffic_source`;
 `traffic_same_build` says whether they were collected on the library build
 this run loaded (the file records its hash).
-cpu_baseline (rank 0, N = 1): the oracle (C restatement of the reference
+cpu_baseline (--full, rank 0, N = 1): the oracle (C restatement of the reference
 arithmetic) over the full single-GPU scene for --cpu-steps steps from t = 0,
 on the host-core share (OMP_NUM_THREADS if set, else the affinity mask) and
 on one core, with the host's nproc / affinity / CPU model; `reference_loop`
@@ -90,9 +98,27 @@ def parse():
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c4", "c5"])
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the "
+                         "accuracy run against it (one GPU), the per-launch kernel timing run (several GPUs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline / accuracy")
     ap.add_argument("--cpu-steps", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step as DIR/qpos.npy and DIR/qvel.npy")
     return ap.parse_args()
+
+
+def dump_outputs(path: str, q, v) -> None:
+    """The arrays a caller of the timed path receives after its last step
+    (ShardedWorld.gather_state: qpos (n, 7), qvel (n, 6)), whole, in the
+    world's precision.  C3 in fp64 is 6.8 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("qpos", q), ("qvel", v)):
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # per-config World arguments: C4's rows slide into pile-ups after ~550 steps
@@ -456,21 +482,28 @@ def main():
         elapsed = float(t.item())
         if not check(sw, done + 2 * args.steps):
             raise SystemExit("bench: the sharded run diverged from the single-World run during the timed steps")
+    if args.dump_outputs:
+        q_out, v_out = sw.gather_state()     # collective for N > 1
+        if rank == 0:
+            dump_outputs(args.dump_outputs, q_out, v_out)
 
     # roofline: average step-kernel launch duration.  One rank: the timed
     # region is exactly K back-to-back step-kernel launches (graph replay),
     # so HIP events around it / K.  Several ranks: a step also runs the
-    # exchange, so time each step-kernel launch with its own event pair.
+    # exchange, so time each step-kernel launch with its own event pair
+    # over a run of its own (--full only).
     if P == 1:
         avg_ms, launches, timing = region_ms / args.steps, args.steps, "HIP events around the timed region / K"
-    else:
+    elif args.full:
         w.kernel_timing(True)
         sw.step(args.steps)
         sw.sync()
         avg_ms, launches = w.kernel_timing(False)
         timing = "HIP event pair around each step-kernel launch (second run of K steps)"
+    else:
+        avg_ms, launches, timing = None, 0, "not timed (--full times each step-kernel launch over a second run)"
     bytes_per_launch = w.bytes_per_body_step * w.n_owned
-    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms else 0.0
     form, clean = region_form(st0, st1, args.steps) if P == 1 else (st1.get("hashed_form", st1.get("form")), True)
     traffic, traffic_lower, traffic_src, traffic_same_build = traffic_from_profiles(
         args.config, args.dtype, P, args.scaling, "_tile" if form == 5 else "")
@@ -513,7 +546,7 @@ def main():
                      "timing": timing,
                      "algorithmic_bytes_per_launch": bytes_per_launch},
     }
-    if rank == 0 and P == 1 and not args.no_cpu_baseline:
+    if rank == 0 and P == 1 and args.full and not args.no_cpu_baseline:
         w.close()
         base, ref = cpu_baseline(args.config, args.cpu_steps)
         line["cpu_baseline"] = base

@@ -19,9 +19,9 @@ if [ -z "${SKIP_PMC:-}" ]; then
   cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
 fi
 step bench-f32
-timeout -k 10 600 python bench.py --dtype f32 > $OUT/bench_c3_f32.json 2> $OUT/bench_c3_f32.err || { tail -5 $OUT/bench_c3_f32.err; exit 1; }
+timeout -k 10 600 python bench.py --full --dtype f32 > $OUT/bench_c3_f32.json 2> $OUT/bench_c3_f32.err || { tail -5 $OUT/bench_c3_f32.err; exit 1; }
 step bench-c2
-timeout -k 10 600 python bench.py --config c2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err || { tail -5 $OUT/bench_c2.err; exit 1; }
+timeout -k 10 600 python bench.py --full --config c2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err || { tail -5 $OUT/bench_c2.err; exit 1; }
 step rocprofv3
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- \
     python bench.py --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || { tail -5 $OUT/prof.err; exit 1; }

@@ -34,15 +34,15 @@ if [ "${SKIP_PMC:-0}" != 1 ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
   step bench-c3
-  timeout -k 10 600 python bench.py > $OUT/bench_c3_f64.json 2> $OUT/bench_c3_f64.err || { tail -5 $OUT/bench_c3_f64.err; exit 1; }
+  timeout -k 10 600 python bench.py --full > $OUT/bench_c3_f64.json 2> $OUT/bench_c3_f64.err || { tail -5 $OUT/bench_c3_f64.err; exit 1; }
   cat $OUT/bench_c3_f64.json | cut -c1-400
   step bench-c3-k20
-  timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c3_k20.json 2> $OUT/bench_c3_k20.err || { tail -5 $OUT/bench_c3_k20.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c3_k20.json 2> $OUT/bench_c3_k20.err || { tail -5 $OUT/bench_c3_k20.err; exit 1; }
   cat $OUT/bench_c3_k20.json | cut -c1-400
   for c in "--dtype f32:c3_f32" "--config c2:c2_f64" "--config c4:c4_f64" "--config c5:c5_f64"; do
     a=${c%%:*}; n=${c##*:}
     step bench $n
-    timeout -k 10 600 python bench.py $a > $OUT/bench_$n.json 2> $OUT/bench_$n.err || { tail -5 $OUT/bench_$n.err; exit 1; }
+    timeout -k 10 600 python bench.py --full $a > $OUT/bench_$n.json 2> $OUT/bench_$n.err || { tail -5 $OUT/bench_$n.err; exit 1; }
     cat $OUT/bench_$n.json | cut -c1-300
   done
   step rocprofv3
@@ -51,7 +51,7 @@ if [ "${SKIP_BENCH:-0}" != 1 ]; then
   find $OUT/prof -name '*kernel_stats.csv' -exec head -6 {} \;
   step rocprofv3-driver-shape
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_driver -o bench -- \
-      python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/prof_driver_bench.json 2> $OUT/prof_driver.err || { tail -5 $OUT/prof_driver.err; exit 1; }
+      python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/prof_driver_bench.json 2> $OUT/prof_driver.err || { tail -5 $OUT/prof_driver.err; exit 1; }
   find $OUT/prof_driver -name '*kernel_stats.csv' -exec head -6 {} \;
 fi
 echo "ALL DONE"

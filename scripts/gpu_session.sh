@@ -19,10 +19,10 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
   step bench
-  timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
   cat $OUT/bench.json
   step bench-driver-shape
-  timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err || { tail -5 $OUT/bench_k20.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err || { tail -5 $OUT/bench_k20.err; exit 1; }
   cat $OUT/bench_k20.json
 fi
 if [ -n "${LIBS:-}" ]; then

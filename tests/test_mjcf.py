@@ -9,10 +9,10 @@ import pytest
 
 from rbhip import mjcf, scenes
 
-REF_MODELS = "/root/reference/models"
+# the reference's four model files, stored as fixtures
+REF_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "models")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkout not present")
 @pytest.mark.parametrize("model,scene", [("sphere", scenes.single_sphere), ("cube", scenes.single_cube),
                                          ("multi_sphere", scenes.multi_sphere4)])
 def test_reference_models_match_pinned_scenes(model, scene):
@@ -24,7 +24,6 @@ def test_reference_models_match_pinned_scenes(model, scene):
     assert sc.dt == ref.dt and sc.names == ref.names
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkout not present")
 def test_ball_collision_model():
     sc = mjcf.load(os.path.join(REF_MODELS, "ball_collision.xml"))
     assert sc.n == 2 and sc.names == ["ball1", "ball2"]

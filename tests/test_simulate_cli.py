@@ -21,13 +21,16 @@ def test_builtin_scenes(name):
     assert sc.n >= 1 and sc.dt > 0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference checkout not present")
+# the reference's four model files, stored as fixtures
+REF_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "models")
+
+
 @pytest.mark.parametrize("name,model", [("single_sphere", "sphere"), ("cube_incline", "cube"),
                                         ("multi_sphere", "multi_sphere"), ("ball_collision", "ball_collision")])
 def test_mjcf_scenes_equal_builtin(name, model):
     """The reference's model files plus the scripts' initial conditions give
     exactly the built-in scenes."""
-    a = simulate.build_scene(name, f"/root/reference/models/{model}.xml")
+    a = simulate.build_scene(name, os.path.join(REF_MODELS, model + ".xml"))
     b = simulate.build_scene(name)
     for f in ("kind", "mass", "inertia", "size", "planes", "qpos0", "qvel0", "gravity"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f
