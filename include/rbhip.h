@@ -318,6 +318,67 @@ int rb_query(rb_world *w, int64_t *n_owned, int64_t *bytes_per_body_step);
 int rb_world_stats(rb_world *w, int64_t *out, int32_t n);
 int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches);
 
+/* ---- batched worlds (librbhip 0.4) ---------------------------------------- */
+/* Many small independent scenes ("environments") stepped by one launch: a
+ * parameter sweep, an ensemble of initial conditions, a domain-randomised
+ * batch of the reference's scenes (1 to 4 bodies each).  A batch is n_envs
+ * replicas of a template environment of M = n_bodies <= 64 bodies; planes,
+ * gravity, dt, the contact threshold and the normal convention are per
+ * batch, restitution / friction / body constants / state per environment.
+ * An environment steps bit-identically to an rb_world of the same scene.
+ * Arrays are environment-major: body k of environment e at row e*M + k.
+ * Not covered (use rb_world): applied forces, contact recording, caller
+ * streams and asynchronous stepping, sharding, box-involved pairs (a box is
+ * accepted only as the single body of its environment), the two-ball law,
+ * per-environment planes or gravity, more than 64 bodies per environment.
+ * A batch handle is not thread-safe; every call is synchronous.
+ *
+ * A step launch runs at most RB_BATCH_CHUNK steps (a bound on kernel duration
+ * on a shared device); longer runs are several launches, with the same
+ * result however a run is cut into launches or calls. */
+#define RB_BATCH_CHUNK 256
+typedef struct rb_batch rb_batch;
+/* Replaces one MjModel/MjData pair per scene variant (as rb_world_create:
+ * collision.py:56, multi_sphere_bounce.py:42).  scene: the template
+ * environment (n_bodies = M in 1..64, world_size 1, rank 0; max_partners and
+ * bucket_capacity unused: every body may touch all others), replicated
+ * n_envs times.  RB_EUNSUPPORTED for a template with a box body and more
+ * than one body. */
+int  rb_batch_create(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs);
+void rb_batch_destroy(rb_batch *b);
+/* Per-environment restitution / friction, [n_envs] each; NULL = use the
+ * scalar given to rb_batch_step.  Replaces the per-scene constants of
+ * src/config/sim_overrides.py:1-28 (one run of the reference per value). */
+int  rb_batch_set_params(rb_batch *b, const double *restitution, const double *friction);
+/* Per-environment body constants: mass [E*M], inertia [E*M*3], size [E*M*3]
+ * (as rb_scene_desc; kinds stay the template's); NULL = keep.  Replaces
+ * model.body_mass / body_inertia / geom_size of a per-variant model
+ * (collision.py:58-62). */
+int  rb_batch_set_bodies(rb_batch *b, const double *mass, const double *inertia, const double *size);
+/* qpos [n*M*7], qvel [n*M*6] for the environments listed in env_ids[n]
+ * (distinct; NULL = all n_envs, in order, n = n_envs).  set clears the listed
+ * environments' failed status and step count (a per-environment reset).
+ * Replaces the reads/writes of data.qpos / data.qvel at collision.py:60-65,
+ * :97-100 and multi_sphere_bounce.py:50-51, :85-88, per environment. */
+int  rb_batch_set_state(rb_batch *b, const int64_t *env_ids, int64_t n, const double *qpos, const double *qvel);
+int  rb_batch_get_state(rb_batch *b, const int64_t *env_ids, int64_t n, double *qpos, double *qvel);
+/* nsteps reference steps of every environment: the per-frame loop of
+ * custom_step_multi_sphere (multi_sphere_bounce.py:42-92), i.e.
+ * custom_step_with_contacts (collision.py:56-102) per body, per environment.
+ * Synchronous.  An environment with a non-finite or out-of-range body
+ * position (the check of rb_step) fails alone: it is not advanced by that
+ * step or any later one — its state stays the start state of the failing
+ * step — until rb_batch_set_state resets it.  Healthy environments are
+ * always stepped to the end.  *n_failed = environments failed so far; with
+ * n_failed == NULL a failed environment makes the call return RB_EDOM (after
+ * stepping the rest). */
+int  rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double restitution, double friction,
+                   double contact_threshold, int64_t *n_failed);
+/* code [n_envs] (RB_OK | RB_EDOM), steps_done [n_envs] (steps completed since
+ * the environment's last rb_batch_set_state); either may be NULL.  No
+ * reference counterpart (the reference raises from inside its one scene). */
+int  rb_batch_status(rb_batch *b, int32_t *code, int64_t *steps_done);
+
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do
  * nothing; mode 1 returns RB_EUNSUPPORTED.  The step forms are chosen by the

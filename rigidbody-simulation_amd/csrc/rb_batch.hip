@@ -1,0 +1,263 @@
+// rb_batch.hip — batched worlds: many small independent scenes (environments)
+// of M <= 64 bodies each, stepped by one launch (rb_batch_* in include/rbhip.h).
+//
+// Body b of environment e is global slot g = e * M + b; state and constants
+// are struct-of-arrays rows of length E * M.  One lane per body, a wave
+// (= one 64-thread workgroup) holds floor(64 / M) whole environments, so an
+// environment never spans two waves and all synchronisation is wave-level.
+//
+// No broadphase: the partners of a body are found by testing every other
+// body of its own environment (at most 63) against the step-start snapshots,
+// which ping-pong in LDS.  A launch loads the 13 state values and the
+// constants of a body once, runs up to RB_BATCH_CHUNK steps in registers and
+// stores once.  Each step is body_update's sequence (rb_kernels.hip) built
+// from the same functions (rb_device.hpp, rb_body.hpp), so an environment
+// steps bit-identically to a world of the same scene.
+#include "rb_device.hpp"
+#include "rb_grid.hpp"
+#include "rb_internal.hpp"
+#include "rb_body.hpp"
+
+namespace rb {
+
+// BOX: the template environment is one box (M == 1); else spheres only
+template <typename T, bool BOX>
+__global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> p) {
+    __shared__ Snap<T> s_snap[2][BATCH_BLOCK];
+    __shared__ int32_t s_fail[BATCH_BLOCK];      // per environment of the wave; sticky within a launch
+
+    const int lane = threadIdx.x;
+    const int M = p.M;
+    const int epw = BATCH_BLOCK / M;             // whole environments per wave
+    const int el_raw = lane / M;
+    const int b = lane - el_raw * M;             // body within the environment
+    // lanes past the wave's last whole environment, or past the batch, are
+    // idle: they run along on slot 0's data and store nothing
+    const bool active = el_raw < epw && (int64_t)blockIdx.x * epw + el_raw < p.E;
+    const int el = active ? el_raw : 0;          // environment within the wave
+    const int64_t env = (int64_t)blockIdx.x * epw + el;
+    const int64_t g = active ? env * M + b : 0;
+    const int ebase = el * M;                    // the environment's first lane
+
+    // ---- load once ---------------------------------------------------------
+    const Snap<T> self = p.snap[g];
+    V3<T> x = {self.x, self.y, self.z};
+    const T bi = self.r;
+    Q4<T> q = {p.st.qw()[g], p.st.qx()[g], p.st.qy()[g], p.st.qz()[g]};
+    V3<T> v = {p.st.vx()[g], p.st.vy()[g], p.st.vz()[g]};
+    V3<T> w = {p.st.wx()[g], p.st.wy()[g], p.st.wz()[g]};
+    const T m = p.cs.mass()[g];
+    const V3<T> I = {p.cs.ix()[g], p.cs.iy()[g], p.cs.iz()[g]};
+    const V3<T> sz = {p.cs.sx()[g], BOX ? p.cs.sy()[g] : T(0), BOX ? p.cs.sz()[g] : T(0)};
+    const int64_t ev = active ? env : 0;
+    // an environment that failed in an earlier launch is not advanced
+    bool failed = !active || p.code[ev] != 0;
+    int32_t done = 0;
+
+    // the per-step constants solve_contact / apply_force read (rb_body.hpp)
+    StepParams<T> sp;
+    sp.xfrc = nullptr;
+    sp.rec_count = nullptr;
+    sp.S = 0;
+    sp.g[0] = p.g[0]; sp.g[1] = p.g[1]; sp.g[2] = p.g[2];
+    sp.dt = p.dt;
+    sp.thr = p.thr;
+    sp.e = p.env_e ? p.env_e[ev] : p.e;
+    sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
+    sp.oriented = p.oriented;
+
+    s_fail[lane] = 0;
+    s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
+    __syncthreads();
+
+    for (int s = 0; s < p.k; ++s) {
+        const Snap<T> *cur = s_snap[s & 1];
+        Snap<T> *nxt = s_snap[(s + 1) & 1];
+        int32_t cx, cy, cz;
+        bool bad = !cell_of(x.x, x.y, x.z, p.inv_cs, cx, cy, cz);     // the step-start position
+
+        V3<T> vn = v, wn = w;
+        LazyInvI<T> invI;
+        invI.I = I;
+        invI.q = q;
+        // ---- a4: gravity (collision.py:66-70; no applied forces here) -------
+        apply_force<T, false>(sp, 0, m, invI, vn, wn);
+        const T kk = impulse_k(m);
+
+        // ---- K2: plane contacts, plane order --------------------------------
+        if constexpr (!BOX) {
+            for (int pl = 0; pl < p.n_planes; ++pl) {
+                const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
+                const V3<T> pp = {p.pp[pl][0], p.pp[pl][1], p.pp[pl][2]};
+                Contact<T> con;
+                if (!plane_sphere(pn, pp, x, sz.x, con)) continue;
+                solve_contact(sp, con, x, con.frame, m, kk, invI, vn, wn);
+            }
+        } else {
+            const M3<T> Mb = mj_body_mat(q);
+            for (int pl = 0; pl < p.n_planes; ++pl) {
+                const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
+                const V3<T> dif = {x.x - p.pp[pl][0], x.y - p.pp[pl][1], x.z - p.pp[pl][2]};
+                const T dist = mj_dot(dif, pn);
+                int cnt = 0;
+                for (int c = 0; c < 8 && cnt < 4; ++c) {
+                    Contact<T> con;
+                    if (!plane_box_corner(pn, x, dist, Mb, sz, c, con)) continue;
+                    ++cnt;
+                    solve_contact(sp, con, x, con.frame, m, kk, invI, vn, wn);
+                }
+            }
+        }
+
+        // ---- K2: every other body of the environment, ascending id ----------
+        if constexpr (!BOX) {
+            for (int j = 0; j < M; ++j) {
+                if (j == b) continue;
+                const Snap<T> sj = cur[ebase + j];
+                const V3<T> cj = {sj.x, sj.y, sj.z};
+                if (!sphere_sphere_hit(x, sz.x, cj, sj.r)) continue;
+                Contact<T> con;
+                V3<T> n;
+                if (b < j) {                        // this body is geom1
+                    sphere_sphere(x, sz.x, cj, sj.r, con);
+                    n = sp.oriented ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
+                } else {
+                    sphere_sphere(cj, sj.r, x, sz.x, con);
+                    n = con.frame;
+                }
+                solve_contact(sp, con, x, n, m, kk, invI, vn, wn);
+            }
+        }
+
+        // ---- K3: integrate (collision.py:90-100) ----------------------------
+        V3<T> xn = x;
+        Q4<T> qn;
+        integrate_pose(xn, qn, q, vn, wn, sp.dt);
+        bad = bad || !cell_of(xn.x, xn.y, xn.z, p.inv_cs, cx, cy, cz);
+
+        // a failing body fails its environment: none of its bodies advances
+        // (the snapshots a failed environment leaves in LDS are read by its
+        // own lanes only, which commit nothing from then on)
+        if (bad && active) s_fail[el] = 1;
+        nxt[lane] = Snap<T>{xn.x, xn.y, xn.z, bi};
+        __syncthreads();
+        failed = failed || s_fail[el] != 0;
+        if (!failed) {
+            x = xn; q = qn; v = vn; w = wn;
+            ++done;
+        }
+    }
+
+    // ---- store once ------------------------------------------------------------
+    if (!active) return;
+    if (done > 0) {
+        p.snap[g] = Snap<T>{x.x, x.y, x.z, bi};
+        p.st.qw()[g] = q.w; p.st.qx()[g] = q.x; p.st.qy()[g] = q.y; p.st.qz()[g] = q.z;
+        p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
+        p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
+    }
+    if (b == 0) {
+        if (done > 0) p.steps_done[env] += done;
+        if (done < p.k && p.code[env] == 0) p.code[env] = BATCH_EDOM;
+    }
+}
+
+// rb_batch_set_state / rb_batch_get_state for a list of environments: row t
+// of the caller's arrays is body t % M of environment ids[t / M].  (All
+// environments in order: state_in_kernel / state_out_kernel, rb_kernels.hip.)
+template <typename T>
+__global__ __launch_bounds__(256) void batch_state_in_kernel(StateIO<T> p, const int64_t *ids, int64_t rows, int32_t M) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= rows) return;
+    const int64_t g = ids[t / M] * M + t % M;
+    const double *q = p.qpos + 7 * t, *v = p.qvel + 6 * t;
+    p.snap[g] = Snap<T>{(T)q[0], (T)q[1], (T)q[2], p.bound[g]};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) p.st.row(d)[g] = (T)q[3 + d];
+#pragma unroll
+    for (int d = 0; d < 6; ++d) p.st.row(4 + d)[g] = (T)v[d];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) p.st.row(10 + d)[g] = (T)q[d];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void batch_state_out_kernel(StateIO<T> p, const int64_t *ids, int64_t rows, int32_t M) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= rows) return;
+    const int64_t g = ids[t / M] * M + t % M;
+    double *q = p.qpos + 7 * t, *v = p.qvel + 6 * t;
+    const Snap<T> s = p.snap[g];
+    q[0] = (double)s.x; q[1] = (double)s.y; q[2] = (double)s.z;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) q[3 + d] = (double)p.st.row(d)[g];
+#pragma unroll
+    for (int d = 0; d < 6; ++d) v[d] = (double)p.st.row(4 + d)[g];
+}
+
+// a per-environment reset (rb_batch_set_state): status and step count of the
+// listed environments (ids == nullptr: the first n)
+__global__ __launch_bounds__(256) void batch_reset_kernel(int32_t *code, int64_t *steps_done, const int64_t *ids, int64_t n) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int64_t e = ids ? ids[t] : t;
+    code[e] = 0;
+    steps_done[e] = 0;
+}
+
+__global__ __launch_bounds__(256) void batch_count_kernel(const int32_t *code, int64_t E, int32_t *out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < E && code[e] != 0) atomicAdd(out, 1);
+}
+
+// new bounding radii (rb_batch_set_bodies) into the snapshots
+template <typename T> __global__ __launch_bounds__(256) void batch_bound_kernel(Snap<T> *snap, const T *bound, int64_t N) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < N) snap[g].r = bound[g];
+}
+
+static unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, hipStream_t s) {
+    if (p.E <= 0 || p.k <= 0) return hipSuccess;
+    const int64_t epw = BATCH_BLOCK / p.M;
+    const unsigned blocks = (unsigned)((p.E + epw - 1) / epw);
+    if (box) hipLaunchKernelGGL((batch_step_kernel<T, true>), dim3(blocks), dim3(BATCH_BLOCK), 0, s, p);
+    else hipLaunchKernelGGL((batch_step_kernel<T, false>), dim3(blocks), dim3(BATCH_BLOCK), 0, s, p);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_batch_state_in(const StateIO<T> &p, const int64_t *ids, int64_t n, int32_t M, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((batch_state_in_kernel<T>), dim3(blocks256(n * M)), dim3(256), 0, s, p, ids, n * M, M);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_batch_state_out(const StateIO<T> &p, const int64_t *ids, int64_t n, int32_t M, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((batch_state_out_kernel<T>), dim3(blocks256(n * M)), dim3(256), 0, s, p, ids, n * M, M);
+    return hipGetLastError();
+}
+hipError_t launch_batch_reset(int32_t *code, int64_t *steps_done, const int64_t *ids, int64_t n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(batch_reset_kernel, dim3(blocks256(n)), dim3(256), 0, s, code, steps_done, ids, n);
+    return hipGetLastError();
+}
+hipError_t launch_batch_count(const int32_t *code, int64_t E, int32_t *out, hipStream_t s) {
+    hipLaunchKernelGGL(batch_count_kernel, dim3(blocks256(E)), dim3(256), 0, s, code, E, out);
+    return hipGetLastError();
+}
+template <typename T> hipError_t launch_batch_bound(Snap<T> *snap, const T *bound, int64_t N, hipStream_t s) {
+    hipLaunchKernelGGL((batch_bound_kernel<T>), dim3(blocks256(N)), dim3(256), 0, s, snap, bound, N);
+    return hipGetLastError();
+}
+
+template hipError_t launch_batch_step<double>(const BatchParams<double> &, bool, hipStream_t);
+template hipError_t launch_batch_step<float>(const BatchParams<float> &, bool, hipStream_t);
+template hipError_t launch_batch_state_in<double>(const StateIO<double> &, const int64_t *, int64_t, int32_t, hipStream_t);
+template hipError_t launch_batch_state_in<float>(const StateIO<float> &, const int64_t *, int64_t, int32_t, hipStream_t);
+template hipError_t launch_batch_state_out<double>(const StateIO<double> &, const int64_t *, int64_t, int32_t, hipStream_t);
+template hipError_t launch_batch_state_out<float>(const StateIO<float> &, const int64_t *, int64_t, int32_t, hipStream_t);
+template hipError_t launch_batch_bound<double>(Snap<double> *, const double *, int64_t, hipStream_t);
+template hipError_t launch_batch_bound<float>(Snap<float> *, const float *, int64_t, hipStream_t);
+
+}  // namespace rb

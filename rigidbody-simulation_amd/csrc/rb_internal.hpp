@@ -415,6 +415,37 @@ template <typename T> hipError_t launch_ball_step(const StepParams<T> &p, int ma
 template <typename T> hipError_t launch_ball_prime(const StepParams<T> &p, hipStream_t s);
 template <typename T> hipError_t launch_kat_pair_impulse(int64_t n, const double *in, double *out, hipStream_t s);
 
+// ---- batched worlds (rb_batch.hip) -----------------------------
+// E independent environments of M <= 64 bodies; body b of environment e is
+// slot e * M + b of every row.  One lane per body, one wave per workgroup,
+// floor(64 / M) whole environments per wave.
+constexpr int BATCH_BLOCK = 64;          // threads per workgroup: one wave
+constexpr int BATCH_CHUNK = 256;         // most steps of one launch (RB_BATCH_CHUNK, include/rbhip.h)
+constexpr int32_t BATCH_EDOM = -33;      // RB_EDOM, as the status word records it
+template <typename T> struct BatchParams {
+    Snap<T> *snap;                       // [E * M] x y z, bounding radius
+    BodyState<T> st;                     // rows of E * M
+    BodyConsts<T> cs;                    // rows of E * M (kind unused: the template's kinds are uniform)
+    const T *env_e, *env_mu;             // [E] restitution / friction, or nullptr: the scalars below
+    int32_t *code;                       // [E] 0 | BATCH_EDOM
+    int64_t *steps_done;                 // [E] steps completed since the environment's last set_state
+    int64_t E;
+    int32_t M, k;                        // bodies per environment; steps of this launch (<= BATCH_CHUNK)
+    int32_t n_planes, oriented;
+    T pn[MAX_PLANES][3], pp[MAX_PLANES][3];
+    T g[3];
+    T dt, e, mu, thr;
+    T inv_cs;                            // 1 / (4 rmax 1.001): the worlds' cell size, for the position check
+};
+template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, hipStream_t s);
+template <typename T>
+hipError_t launch_batch_state_in(const StateIO<T> &p, const int64_t *ids, int64_t n, int32_t M, hipStream_t s);
+template <typename T>
+hipError_t launch_batch_state_out(const StateIO<T> &p, const int64_t *ids, int64_t n, int32_t M, hipStream_t s);
+hipError_t launch_batch_reset(int32_t *code, int64_t *steps_done, const int64_t *ids, int64_t n, hipStream_t s);
+hipError_t launch_batch_count(const int32_t *code, int64_t E, int32_t *out, hipStream_t s);
+template <typename T> hipError_t launch_batch_bound(Snap<T> *snap, const T *bound, int64_t N, hipStream_t s);
+
 // threads per step-kernel workgroup (the Makefile's WIDE_BLOCK sets it for
 // the wide form's unit alone)
 #ifndef RB_STEP_BLOCK

@@ -76,6 +76,14 @@ SIGNATURES = {
     "rb_kernel_timing": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "rb_tile_config": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _I64]),
     "rb_world_stats": (C.c_int, [_P, C.POINTER(_I64), _I32]),
+    "rb_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), _I64]),
+    "rb_batch_destroy": (None, [_P]),
+    "rb_batch_set_params": (C.c_int, [_P, _P, _P]),
+    "rb_batch_set_bodies": (C.c_int, [_P, _P, _P, _P]),
+    "rb_batch_set_state": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "rb_batch_get_state": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "rb_batch_step": (C.c_int, [_P, _I64, _D, _D, _D, _D, C.POINTER(_I64)]),
+    "rb_batch_status": (C.c_int, [_P, _P, _P]),
 }
 
 # rb_world_stats indices (include/rbhip.h RB_STAT_*)

@@ -1,0 +1,137 @@
+"""BatchWorld: many small independent scenes on one MI355X, one launch per
+step chunk (rb_batch_* in include/rbhip.h).
+
+The reference's scenes hold 1 to 4 bodies and are studied one knob per run
+(src/config/sim_overrides.py; the velocity variants under
+data/plots/single_sphere/).  A BatchWorld is n_envs replicas of one such
+scene, each with its own restitution, friction, body constants and state;
+every environment steps bit-identically to a World of the same scene.
+Arrays are environment-major: (E, M, 7) / (E, M, 6).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from .scenes import Scene
+
+
+class BatchWorld:
+    def __init__(self, scene: Scene, n_envs: int, device: int = 0, dtype: str = "f64",
+                 normal_convention: Optional[str] = None):
+        """scene: the template environment (1..64 bodies; a box only alone),
+        replicated n_envs times with the scene's initial state."""
+        L = _lib.load()
+        self.scene = scene
+        self.dtype = dtype
+        self.n_envs, self.n_bodies = int(n_envs), scene.n
+        nc = normal_convention or scene.normal_convention
+        kind = np.ascontiguousarray(scene.kind, np.int32)
+        mass = np.ascontiguousarray(scene.mass, np.float64)
+        inertia = np.ascontiguousarray(scene.inertia, np.float64)
+        size = np.ascontiguousarray(scene.size, np.float64)
+        planes = np.ascontiguousarray(scene.planes, np.float64)
+        d = _lib.SceneDesc()
+        d.n_bodies = scene.n
+        d.n_planes = planes.shape[0]
+        d.dtype = _lib.RB_F64 if dtype == "f64" else _lib.RB_F32
+        d.normal_convention = _lib.RB_NORMAL_RAW if nc == "raw" else _lib.RB_NORMAL_ORIENTED
+        d.device, d.rank, d.world_size = device, 0, 1
+        d.kind, d.mass = _lib.ptr(kind), _lib.ptr(mass)
+        d.inertia, d.size = _lib.ptr(inertia), _lib.ptr(size)
+        d.planes = _lib.ptr(planes) if d.n_planes else None
+        for k in range(3):
+            d.gravity[k] = float(scene.gravity[k])
+        h = C.c_void_p()
+        self._h = None
+        _lib.check(L.rb_batch_create(C.byref(h), C.byref(d), self.n_envs), "rb_batch_create")
+        self._h = h
+        self._L = L
+        E, M = self.n_envs, self.n_bodies
+        self.set_state(np.broadcast_to(scene.qpos0, (E, M, 7)), np.broadcast_to(scene.qvel0, (E, M, 6)))
+
+    # ---- lifetime ---------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rb_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- per-environment constants ----------------------------------------
+    def _arr(self, a, shape):
+        return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), shape))
+
+    def set_params(self, restitution=None, friction=None):
+        """Per-environment restitution / friction, (E,) each; None: the
+        scalar given to step()."""
+        e = self._arr(restitution, (self.n_envs,))
+        mu = self._arr(friction, (self.n_envs,))
+        _lib.check(self._L.rb_batch_set_params(self._h, _lib.ptr(e), _lib.ptr(mu)), "rb_batch_set_params")
+
+    def set_bodies(self, mass=None, inertia=None, size=None):
+        """Per-environment body constants: mass (E, M), inertia (E, M, 3),
+        size (E, M, 3); None: keep."""
+        E, M = self.n_envs, self.n_bodies
+        m, i, s = self._arr(mass, (E, M)), self._arr(inertia, (E, M, 3)), self._arr(size, (E, M, 3))
+        _lib.check(self._L.rb_batch_set_bodies(self._h, _lib.ptr(m), _lib.ptr(i), _lib.ptr(s)), "rb_batch_set_bodies")
+
+    # ---- state --------------------------------------------------------------
+    def _envs(self, envs):
+        if envs is None:
+            return None, self.n_envs
+        ids = np.ascontiguousarray(envs, np.int64).reshape(-1)
+        return ids, ids.shape[0]
+
+    def set_state(self, qpos, qvel, envs=None):
+        """qpos (n, M, 7), qvel (n, M, 6) for the environments in envs (None:
+        all, in order).  Clears the failed status of those environments."""
+        ids, n = self._envs(envs)
+        q = np.ascontiguousarray(qpos, np.float64).reshape(n, self.n_bodies, 7)
+        v = np.ascontiguousarray(qvel, np.float64).reshape(n, self.n_bodies, 6)
+        _lib.check(self._L.rb_batch_set_state(self._h, _lib.ptr(ids), n, _lib.ptr(q), _lib.ptr(v)),
+                   "rb_batch_set_state")
+
+    def get_state(self, envs=None):
+        """(qpos (n, M, 7), qvel (n, M, 6)) of the environments in envs (None: all)."""
+        ids, n = self._envs(envs)
+        q = np.zeros((n, self.n_bodies, 7))
+        v = np.zeros((n, self.n_bodies, 6))
+        _lib.check(self._L.rb_batch_get_state(self._h, _lib.ptr(ids), n, _lib.ptr(q), _lib.ptr(v)),
+                   "rb_batch_get_state")
+        return q, v
+
+    # ---- stepping -----------------------------------------------------------
+    def _params(self, dt, restitution, friction, threshold):
+        sc = self.scene
+        return (sc.dt if dt is None else dt, sc.restitution if restitution is None else restitution,
+                sc.friction if friction is None else friction,
+                sc.threshold if threshold is None else threshold)
+
+    def step(self, nsteps: int = 1, dt=None, restitution=None, friction=None, threshold=None) -> int:
+        """Step every healthy environment nsteps times; returns how many
+        environments have failed so far (status())."""
+        p = self._params(dt, restitution, friction, threshold)
+        nf = C.c_int64()
+        _lib.check(self._L.rb_batch_step(self._h, int(nsteps), *p, C.byref(nf)), "rb_batch_step")
+        return nf.value
+
+    def status(self):
+        """(code (E,) int32: 0 or RB_EDOM (-33); steps_done (E,) int64)."""
+        code = np.zeros(self.n_envs, np.int32)
+        done = np.zeros(self.n_envs, np.int64)
+        _lib.check(self._L.rb_batch_status(self._h, _lib.ptr(code), _lib.ptr(done)), "rb_batch_status")
+        return code, done
