@@ -314,7 +314,17 @@ int rb_query(rb_world *w, int64_t *n_owned, int64_t *bytes_per_body_step);
 #define RB_STAT_TILE_ON        17   /* the next run of >= 2 steps would use the tile form */
 #define RB_STAT_HASHED_FORM    18   /* the hashed-cell form (0-4, as RB_STAT_FORM) the world steps with when
                                        the tile form does not */
-#define RB_STATS_COUNT         19
+/* Append epochs (appended counters; sphere-only worlds on one rank stepped by a
+ * wide form): a broadphase table is read by up to RBHIP_TABLE_EPOCH
+ * consecutive steps; all but the last only append the bodies that changed
+ * cell, the last rebuilds the next table from every body.  Worlds without
+ * epochs report 0 for both step counters (and do not wait for the device).
+ * The counters count launches: the steps of a guarded chunk that was rolled
+ * back and replayed are counted twice. */
+#define RB_STAT_APPEND_STEPS   19   /* steps that appended to the table they read */
+#define RB_STAT_REBUILD_STEPS  20   /* steps of a world with epochs that rebuilt the next table */
+#define RB_STAT_TABLE_EPOCH    21   /* RBHIP_TABLE_EPOCH: the longest epoch (1: every step rebuilds) */
+#define RB_STATS_COUNT         22
 int rb_world_stats(rb_world *w, int64_t *out, int32_t n);
 int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches);
 

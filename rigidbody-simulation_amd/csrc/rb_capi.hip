@@ -243,7 +243,14 @@ struct rb_world {
     uint32_t *spill[2] = {};   // [SPILL_LINES x SPILL_LINE_WORDS] ids past full buckets, per table
     void *pos[2] = {};         // [H][LINE_WORDS] Snap<T> bucket slot snapshots
     uint32_t *gen = nullptr;   // [2] generation of the table of each step parity (rb_internal.hpp Table)
-    uint32_t gen_off = 1;      // generation of step c's table = gen_off + c (host bookkeeping; only grows)
+    uint32_t gen_off = 1;      // an upper bound of step c's generation: gen_off + c (host bookkeeping; only
+                               // grows; append steps keep their table's generation, so the device's lag it)
+    // append epochs (rb_internal.hpp Epoch): one allocation — control words
+    // [2] by step parity, crowding flags [2], counters [2] (append steps,
+    // rebuild steps)
+    int32_t epoch_max = EPOCH_DEFAULT;   // RBHIP_TABLE_EPOCH; 1: every step rebuilds its next table
+    uint32_t *ep_mem = nullptr;
+    bool ep_primed = false;        // the last prime() started an epoch schedule
     int32_t *plist = nullptr;      // split form: [MAXP][S] sorted partner ids
     int32_t *plist_cnt = nullptr;  // split form: [S] partner counts
     int32_t *err = nullptr;
@@ -339,6 +346,17 @@ struct rb_world {
 
     int sp() const { return (int)(c % 2); }
 };
+
+// Append epochs: sphere-only worlds on one rank (no exchange, whose ghosts
+// need an insert per step) under the default law, stepped by a wide form.
+namespace {
+int step_form(const rb_world *w);
+bool epoch_eligible(const rb_world *w) {
+    const int form = step_form(w);
+    return w->epoch_max > 1 && w->ep_mem && w->P == 1 && !w->p2p && !w->comm && w->all_spheres && !w->boxes &&
+           w->law == RB_LAW_MUJOCO && !w->plist && (form == FORM_WIDE || form == FORM_WIDE_HELP);   // (plist: the split form)
+}
+}  // namespace
 
 extern "C" {
 static void fit_period(rb_world *w, const double *qpos, bool force = false);   // (below)
@@ -443,6 +461,16 @@ template <typename T> StepParams<T> make_step(rb_world *w, int64_t c, double dt,
         p.rec_dist = dp<T>(w->rec_dist, 0);
         p.maxrec = w->maxrec;
     }
+    if (insert_next && epoch_eligible(w)) {
+        int32_t *crowd = reinterpret_cast<int32_t *>(w->ep_mem + 2);
+        p.ep.ctrl = w->ep_mem + sp;
+        p.ep.ctrl_next = w->ep_mem + (1 - sp);
+        for (int k = 0; k < 2; ++k) { p.ep.line[k] = w->ids[k]; p.ep.spill[k] = w->spill[k]; }
+        p.ep.crowd = crowd + sp;
+        p.ep.crowd_prev = crowd + (1 - sp);
+        p.ep.count = reinterpret_cast<unsigned long long *>(w->ep_mem + 4);
+        p.ep.len_max = w->epoch_max;
+    }
     return p;
 }
 
@@ -486,11 +514,20 @@ int prime(rb_world *w, double dt = 0, double e = 0, double mu = 0) {
                         ? launch_insert<double>(make_insert<double>(w, w->sp(), 0, w->N, 0, 0), w->stream)
                         : launch_insert<float>(make_insert<float>(w, w->sp(), 0, w->N, 0, 0), w->stream);
     HIPCHK(ie);
+    // a fresh epoch: the step reads the table just built (the one of its
+    // parity); the crowding flags of any epoch cut short are dropped
+    w->ep_primed = epoch_eligible(w);
+    if (w->ep_primed) {
+        const uint32_t cw = epoch_word((uint32_t)w->sp(), 0u, std::min((uint32_t)w->epoch_max, EP_START_LEN), false, 0u);
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w->ep_mem + w->sp()), (int)cw, 1, w->stream));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w->ep_mem + 2), 0, 2, w->stream));
+    }
     w->primed = true;
     return RB_OK;
 }
 
-// the per-step kernel form of this world
+// the per-step kernel form of this world (a world keeps it; a switch of
+// form would have to re-prime: the epoch schedule belongs to the wide forms)
 int step_form(const rb_world *w) {
     return w->n_local <= w->coop_max ? (w->n_local <= w->help_max ? FORM_COOP_HELP : FORM_COOP)
            : w->n_local <= w->wide_max ? (w->wide_help ? FORM_WIDE_HELP : FORM_WIDE) : FORM_ONE;
@@ -1348,6 +1385,7 @@ int enqueue_steps(rb_world *w, int64_t nsteps, double dt, double e, double mu, d
     w->state_version += 1;
     w->tile_valid_sp = -1;                           // the hashed forms advance the id-ordered state
     if (int rc = gen_guard(w, nsteps)) return rc;
+    if (epoch_eligible(w) != w->ep_primed) w->primed = false;   // (the table a step reads: the epoch's, or its parity's)
     if (!w->primed || (w->law == RB_LAW_BALLS && (dt != w->prm_dt || e != w->prm_e || mu != w->prm_mu))) {
         int rc = prime(w, dt, e, mu);
         if (rc) return rc;
@@ -1667,7 +1705,7 @@ void free_world(rb_world *w) {
     if (w->io_v_d) (void)hipFree(w->io_v_d);
     for (hipEvent_t &e : w->io_ev)
         if (e) (void)hipEventDestroy(e);
-    void *bufs[] = {w->snap[0], w->snap[1], w->qsnap[0], w->qsnap[1], w->defer_q, w->defer_cnt, w->state, w->consts, w->kind, w->xfrc, w->gen,
+    void *bufs[] = {w->snap[0], w->snap[1], w->qsnap[0], w->qsnap[1], w->defer_q, w->defer_cnt, w->state, w->consts, w->kind, w->xfrc, w->gen, w->ep_mem,
                     w->ids[0], w->ids[1], w->spill[0], w->spill[1], w->pos[0], w->pos[1], w->plist, w->plist_cnt, w->vel[0], w->vel[1], w->err, w->rec_count, w->rec_partner, w->rec_kind,
                     w->rec_dist};
     for (void *b : bufs)
@@ -1753,6 +1791,7 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     if (const char *ev = getenv("RBHIP_TILE_MIN_BODIES")) w->tile_min_bodies = atoll(ev);
     if (const char *ev = getenv("RBHIP_BOX_OPTIMISTIC")) w->box_opt = atoi(ev) != 0;
     if (const char *ev = getenv("RBHIP_DIAG_OVERFLOW")) w->diag_overflow = atoi(ev);
+    if (const char *ev = getenv("RBHIP_TABLE_EPOCH")) w->epoch_max = std::max(1, std::min(EPOCH_MAX, atoi(ev)));
     // buckets: cooperative worlds (a hash per cell; they also keep a slot
     // snapshot line per bucket) 16 per body; the one-lane and wide forms
     // (linear cell groups, below) 32 per body, so the groups' period spans
@@ -1848,6 +1887,7 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     ALLOC(w->consts, (size_t)w->esz * 8 * w->Npad);
     ALLOC(w->kind, sizeof(int32_t) * w->Npad);
     ALLOC(w->gen, sizeof(uint32_t) * 2);
+    ALLOC(w->ep_mem, sizeof(uint32_t) * 8);
     // Opt-in (RBHIP_SPLIT=1): large scenes step in two kernels (search,
     // update) joined by a partner list; bit-exact with the oracle on the
     // device (tests/test_gpu_parity.py ragged-scene test) but no faster
@@ -1883,7 +1923,7 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
             {w->ids[0], sizeof(uint32_t) * LINE_WORDS * w->H}, {w->ids[1], sizeof(uint32_t) * LINE_WORDS * w->H},
             {w->spill[0], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES},
             {w->spill[1], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES},
-            {w->gen, sizeof(uint32_t) * 2}, {w->err, sizeof(int32_t)}, {w->defer_cnt, sizeof(int32_t) * 2}};
+            {w->gen, sizeof(uint32_t) * 2}, {w->ep_mem, sizeof(uint32_t) * 8}, {w->err, sizeof(int32_t)}, {w->defer_cnt, sizeof(int32_t) * 2}};
         for (const auto &z : zero)
             if (z.first && hipMemsetAsync(z.first, 0, z.second, w->stream) != hipSuccess)
                 return bail(fail(RB_ENODEV, "hipMemsetAsync failed"));
@@ -2496,11 +2536,16 @@ int rb_world_stats(rb_world *w, int64_t *out, int32_t n) {
     if (int rc = finish_pending(w)) return rc;
     const bool tile = tile_eligible(w);
     const int form = tile ? FORM_TILE : step_form(w);
+    // the epoch counters are advanced by the step kernels: read once the
+    // world's work so far is done (only worlds that can have epochs wait)
+    unsigned long long ep_count[2] = {0, 0};
+    if (n > RB_STAT_APPEND_STEPS && epoch_eligible(w)) WCHK(wget(w, ep_count, w->ep_mem + 4, sizeof(ep_count)));
     const int64_t v[RB_STATS_COUNT] = {(int64_t)w->graphs.size(), form, w->box_stats[0], w->box_stats[1], w->refits,
                                        w->table_grows, w->H, (int64_t)w->maxp, w->io_stats[0], w->io_stats[1],
                                        w->tile_stats[0], w->tile_stats[1], w->tile_stats[2], w->tile_stats[3],
                                        (int64_t)w->tile_why_seen, (int64_t)w->tile_ntx * w->tile_nty,
-                                       (int64_t)w->tile_tc, tile && w->tile_skip == 0 ? 1 : 0, step_form(w)};
+                                       (int64_t)w->tile_tc, tile && w->tile_skip == 0 ? 1 : 0, step_form(w),
+                                       (int64_t)ep_count[0], (int64_t)ep_count[1], (int64_t)w->epoch_max};
     for (int32_t k = 0; k < n && k < RB_STATS_COUNT; ++k) out[k] = v[k];
     return n < RB_STATS_COUNT ? n : RB_STATS_COUNT;
 }

@@ -218,13 +218,17 @@ struct Claim {
     int32_t rl;                  // the table's log2 heads per line
 };
 // RL: the table's log2 heads per line when known at compile time (-1: Grid::super)
+// keep: the bucket that already lists the body (append steps, rb_internal.hpp
+// Epoch: a body still in it claims nothing); NO_BUCKET: none
+constexpr uint32_t NO_BUCKET = 0xffffffffu;
 template <int L = LAYOUT_ANY, int RL = -1, typename T>
 __device__ __forceinline__ Claim claim_slot(const Grid<T> &g, const Table<T> &tab, int32_t *err, const Snap<T> &sn,
-                                            uint32_t gen) {
+                                            uint32_t gen, uint32_t keep = NO_BUCKET) {
     int32_t ix = 0, iy = 0, iz = 0;
-    const bool in = cell_of(sn.x, sn.y, sn.z, g.inv_cs, ix, iy, iz);
+    bool in = cell_of(sn.x, sn.y, sn.z, g.inv_cs, ix, iy, iz);
     if (!in) atomicOr(err, ERR_DOMAIN);
     const uint32_t b = bucket_of<L>(ix, iy, iz, g);
+    in = in && b != keep;
     // no defined value when !in (never decoded then): a constant here would
     // make the join select it against the atomic's return, i.e. wait for it
     unsigned long long old = __builtin_nondeterministic_value(0ull);
@@ -579,10 +583,14 @@ __device__ __forceinline__ void sort_partners_bitonic(int32_t *s_id, uint8_t *s_
         }
 }
 
-template <typename T, int MAXP, typename Hit, typename Overlap>
+// EP: the world runs append epochs (rb_internal.hpp Epoch): the id filter
+// and the duplicate handling below are compiled for its launches only, so
+// every other world runs the search as it was.
+template <typename T, int MAXP, bool EP, typename Hit, typename Overlap>
 __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, int32_t i, V3<T> x, int32_t *s_id,
                                                        uint32_t *s_cand, uint8_t *s_didx, Snap<T> *s_hpos, int tid,
-                                                       uint32_t gen, Hit hit, Overlap overlap) {
+                                                       uint32_t gen, const Table<T> &cur, bool appended,
+                                                       uint32_t &b0, Hit hit, Overlap overlap) {
     constexpr int NB = STEP_BLOCK;
     constexpr int QB = WIDE_QBATCH;
     int32_t cx, cy, cz, sx, sy, sz;
@@ -597,7 +605,8 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
     neighbour_buckets<LAYOUT_LINEAR>(p.grid, cx, cy, cz, sx, sy, sz, b);
     constexpr int rl = 2;                         // heads per line: wide-form worlds 4 (rb_capi.hip)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) hd[k] = bucket_head6(p.cur, (uint32_t)CHK(b[k], p.grid.H), rl);
+    for (int k = 0; k < 8; ++k) hd[k] = bucket_head6(cur, (uint32_t)CHK(b[k], p.grid.H), rl);
+    b0 = b[0];                                    // the body's own bucket
     // the head loads issue here, before the body work: left to itself the
     // scheduler hoisted the work (and its waits for the state loads) above
     // them, and the head round trip started only after it
@@ -607,6 +616,15 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
     int32_t n = 0;
     bool more = false;
     uint32_t spm = 0;                                 // buckets with spilled ids
+    // A table that steps append to (rb_internal.hpp Epoch) is read while
+    // bodies of the same launch claim slots in it, so a count may include a
+    // slot whose id is not stored yet.  The slot then holds an id stored
+    // under an older generation, or the zero it was allocated with: a body
+    // of this world, which is tested against its step-start snapshot like
+    // any candidate and so can only be an extra candidate, never a wrong
+    // contact (append epochs are for sphere-only worlds: no stale BOX_FLAG
+    // can defer a body).  Anything else (>= n_global) is treated as absent.
+    [[maybe_unused]] const uint32_t ng = (uint32_t)p.n_global;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         int32_t m = head_count(hd[k].a, gen);
@@ -622,7 +640,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
         {                                                                         \
             const uint32_t t = head6_id<S>(hd[k]);                                \
             s_cand[n * NB + tid] = t;                                             \
-            n += (S < m && (t & ~BOX_FLAG) != (uint32_t)i) ? 1 : 0;               \
+            n += (S < m && (t & ~BOX_FLAG) != (uint32_t)i && (!EP || (t & ~BOX_FLAG) < ng)) ? 1 : 0; \
         }
         RB_WIDE_LIST(0) RB_WIDE_LIST(1) RB_WIDE_LIST(2) RB_WIDE_LIST(3) RB_WIDE_LIST(4) RB_WIDE_LIST(5)
 #undef RB_WIDE_LIST
@@ -690,7 +708,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
 #pragma unroll
                 for (int k = 6; k >= 0; --k)
                     if (t < E[k]) { bk = b[k]; base = k ? E[k - 1] : 0; }
-                tjn[u] = t < e ? xld(slot_word(p.cur, bk, t - base + WIDE_HEAD_IDS, rl)) : (uint32_t)i;
+                tjn[u] = t < e ? xld(slot_word(cur, bk, t - base + WIDE_HEAD_IDS, rl)) : (uint32_t)i;
             }
         };
         load_ids(0);
@@ -698,7 +716,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
         for (int32_t t0 = 0; t0 < e; t0 += QB) {
             uint32_t tj[QB];
 #pragma unroll
-            for (int u = 0; u < QB; ++u) tj[u] = tjn[u];
+            for (int u = 0; u < QB; ++u) tj[u] = (!EP || (tjn[u] & ~BOX_FLAG) < ng) ? tjn[u] : (uint32_t)i;
             Snap<T> sn[QB];
 #pragma unroll
             for (int u = 0; u < QB; ++u) {
@@ -726,6 +744,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
             s_cand[k * NB + tid] = b[k];
             s_cand[(8 + k) * NB + tid] = (uint32_t)c[k];
         }
+        auto known = [&](uint32_t t) { return (!EP || (t & ~BOX_FLAG) < ng) ? t : (uint32_t)i; };
         auto test = [&](const uint32_t (&tj)[QB], const Snap<T> (&sn)[QB], int s0, int32_t ck) {
 #pragma unroll
             for (int u = 0; u < QB; ++u)
@@ -756,7 +775,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
                 while (k < 8 && s >= (int32_t)s_cand[(8 + k) * NB + tid]) { ++k; s = WIDE_HEAD_IDS; }
                 tjn[u] = (uint32_t)i;
                 if (k < 8) {
-                    tjn[u] = xld(slot_word(p.cur, s_cand[k * NB + tid], s, rl));
+                    tjn[u] = known(xld(slot_word(cur, s_cand[k * NB + tid], s, rl)));
                     ++s;
                     any = true;
                 }
@@ -785,7 +804,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
                 Snap<T> sn[QB];
 #pragma unroll
                 for (int u = 0; u < QB; ++u)
-                    tj[u] = s0 + u < ck ? xld(slot_word(p.cur, bk, s0 + u, rl)) : (uint32_t)i;
+                    tj[u] = s0 + u < ck ? known(xld(slot_word(cur, bk, s0 + u, rl))) : (uint32_t)i;
                 gather(tj, sn);
                 test(tj, sn, s0, ck);
             }
@@ -797,9 +816,9 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
 #pragma unroll 1                                      // bucket is a 7+ one: its index is stashed)
         for (int k = 0; k < 8; ++k) {
             if (!((spm >> k) & 1u)) continue;
-            spill_scan(p.cur, gen, s_cand[k * NB + tid], [&](uint32_t t) {
+            spill_scan(cur, gen, s_cand[k * NB + tid], [&](uint32_t t) {
                 const uint32_t j = t & ~BOX_FLAG;
-                if (j == (uint32_t)i) return;
+                if (j == (uint32_t)i || (EP && j >= ng)) return;
                 const Snap<T> sn = xld(p.snap_cur + CHK(j, p.n_global));
                 if (!hit(t, sn)) return;
                 append((int32_t)j, sn);
@@ -815,8 +834,34 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
     // index (the s_hpos slot).  (The rank loop unrolled over the list's
     // capacity measured slower: C4's pile-up 72.0 -> 87.7 us,
     // profiles/r04/rank_unroll_ab_c4.log)
+    // Two partners, the common list of more than one: the two ids read back
+    // and exchanged by one compare (kept in registers from the appends on,
+    // they cost the kernel 12 bytes of scratch per lane).
     if (np_ > WIDE_RANK_MAX) {
         sort_partners_bitonic<MAXP>(s_id, RB_WIDE_LDSPOS ? s_didx : nullptr, NB, tid, np_, nh);
+    } else if (np_ == 2) {
+        const int32_t j0 = s_id[tid], j1 = s_id[NB + tid];
+        const bool sw = j1 < j0;
+        s_id[tid] = sw ? j1 : j0;
+        s_id[NB + tid] = sw ? j0 : j1;
+        if (RB_WIDE_LDSPOS) {
+            s_didx[tid] = sw ? 1 : 0;
+            s_didx[NB + tid] = sw ? 0 : 1;
+        }
+    } else if (EP && appended && np_ > 1) {
+        // (equal ids, an appended table's, rank by position; a loop of its
+        // own: the tie-break in the common one cost C4 0.6 us per step)
+        for (int u = 0; u < np_; ++u) {
+            const int32_t v = s_id[u * NB + tid];
+            int r = 0;
+            for (int q = 0; q < np_; ++q) {
+                const int32_t o = s_id[q * NB + tid];
+                r += (o < v || (o == v && q < u)) ? 1 : 0;
+            }
+            s_cand[r * NB + tid] = (uint32_t)v;
+            if (RB_WIDE_LDSPOS) s_didx[r * NB + tid] = (uint8_t)u;
+        }
+        for (int u = 0; u < np_; ++u) s_id[u * NB + tid] = (int32_t)s_cand[u * NB + tid];
     } else if (np_ > 1) {
         for (int u = 0; u < np_; ++u) {
             const int32_t v = s_id[u * NB + tid];
@@ -828,6 +873,28 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
         for (int u = 0; u < np_; ++u) s_id[u * NB + tid] = (int32_t)s_cand[u * NB + tid];
     } else if (RB_WIDE_LDSPOS && np_ == 1) {
         s_didx[tid] = 0;
+    }
+    // An appended table can list a body twice (its old bucket and its new
+    // one, or one bucket after a move out and back), so a partner can be hit
+    // twice: equal ids are adjacent now, and the second is dropped (with its
+    // discovery index; both snapshots are the same body's).  Here, once per
+    // body, and not where a hit is appended: that loop, inlined at every one
+    // of the search's hit tests, cost 0.7 us per step at C3 in every world.
+    // (A list that overflows max_partners only through its duplicates still
+    // reports the overflow.)
+    if (EP && appended && np_ > 1) {
+        int32_t w = 1;
+        int32_t prev = s_id[tid];
+        for (int u = 1; u < np_; ++u) {
+            const int32_t v = s_id[u * NB + tid];
+            if (v != prev) {
+                s_id[w * NB + tid] = v;
+                if (RB_WIDE_LDSPOS) s_didx[w * NB + tid] = s_didx[u * NB + tid];
+                ++w;
+            }
+            prev = v;
+        }
+        np_ = w;
     }
     STAMP(10);
     if (overflow) atomicOr(p.err, ERR_PARTNER_OVERFLOW);

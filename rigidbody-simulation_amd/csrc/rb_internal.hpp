@@ -189,6 +189,43 @@ struct HaloPush {
     int32_t rank, P;
 };
 
+// Append epochs (wide step kernels): a table is read by up to
+// len consecutive steps.  All but the last of them APPEND: only a body whose
+// bucket changed in the step claims a slot, in the table the step reads and
+// under its generation; its old entry stays.  The last one REBUILDS: every
+// body is inserted into the other table under the next generation, as in a
+// world without epochs.  The schedule lives on the device, one control word
+// per step parity, so captured graphs do not depend on the phase: the step of
+// parity sp reads ctrl[sp], and its block 0 writes ctrl[1 - sp] where it
+// publishes the next step's generation.
+//   bit 0       which table (line[], spill[]) the step reads
+//   bit 1       the step appends (else rebuilds)
+//   bit 2       a body claimed a slot past a bucket's 32-byte head in this epoch (crowding:
+//               the epoch ends with the next step, the one after it has length 1)
+//   bits 8-15   steps that read this table before this one
+//   bits 16-23  the epoch's length
+//   bits 24-31  rebuild steps since the table was primed (saturating): the first EP_START_REBUILDS
+//               epochs are at most EP_START_LEN steps long — a scene just set in motion (C3's first
+//               hundred steps: 6-7 % of the bodies change cell per step) gathers stale entries faster
+//               than the skipped inserts pay (longer epochs lose there, 2 is even)
+constexpr uint32_t EP_TAB = 1u, EP_APPEND = 2u, EP_DIRTY = 4u;
+constexpr int EP_AGE_SHIFT = 8, EP_LEN_SHIFT = 16, EP_START_SHIFT = 24;
+constexpr uint32_t EP_START_REBUILDS = 32, EP_START_LEN = 2;
+constexpr int EPOCH_MAX = 64;                // largest RBHIP_TABLE_EPOCH
+constexpr int EPOCH_DEFAULT = 8;             // (the measured choice)
+__host__ __device__ inline uint32_t epoch_word(uint32_t tab, uint32_t age, uint32_t len, bool dirty, uint32_t start) {
+    return (tab & 1u) | (age + 1u < len ? EP_APPEND : 0u) | (dirty ? EP_DIRTY : 0u) | (age << EP_AGE_SHIFT) |
+           (len << EP_LEN_SHIFT) | (start << EP_START_SHIFT);
+}
+struct Epoch {
+    const uint32_t *ctrl;              // this step's control word; nullptr: no epochs (cur / next as given)
+    uint32_t *ctrl_next;               // the next step's
+    uint32_t *line[2], *spill[2];      // both tables
+    int32_t *crowd, *crowd_prev;       // crowding flag raised by this step's claims / by the step before
+    unsigned long long *count;         // [2] append steps, rebuild steps taken (stats)
+    int32_t len_max;                   // RBHIP_TABLE_EPOCH
+};
+
 template <typename T> struct StepParams {
     // the first 64 bytes hold everything the step's first loads need, so the
     // prologue fetches them with one scalar load
@@ -235,6 +272,7 @@ template <typename T> struct StepParams {
     int32_t *defer_cnt;
     int32_t *defer_reset;
     HaloPush halo;                     // fused halo push (halo-exchanging shards)
+    Epoch ep;                          // append epochs (eligible wide-form worlds)
 };
 
 static_assert(offsetof(StepParams<double>, xfrc) == 64 && offsetof(StepParams<float>, xfrc) == 64,

@@ -114,13 +114,13 @@ __device__ __forceinline__ int32_t search_partners(const StepParams<T> &p, int32
 }
 
 // K1, wide one-lane form (rb_grid.hpp search_buckets_wide)
-template <typename T, int MAXP, bool BOXES, typename Overlap>
+template <typename T, int MAXP, bool BOXES, bool EP, typename Overlap>
 __device__ __forceinline__ int32_t search_partners_wide(const StepParams<T> &p, int32_t i, int32_t kind, V3<T> x,
                                                         T rad, T bi, int32_t *s_id, uint32_t *s_cand, uint8_t *s_didx,
-                                                        Snap<T> *s_hpos, int tid, uint32_t gen, bool &defer,
-                                                        Overlap overlap) {
-    return search_buckets_wide<T, MAXP>(
-        p, i, x, s_id, s_cand, s_didx, s_hpos, tid, gen,
+                                                        Snap<T> *s_hpos, int tid, uint32_t gen, const Table<T> &cur,
+                                                        bool appended, uint32_t &b0, bool &defer, Overlap overlap) {
+    return search_buckets_wide<T, MAXP, EP>(
+        p, i, x, s_id, s_cand, s_didx, s_hpos, tid, gen, cur, appended, b0,
         [&](uint32_t tj, const Snap<T> &s) { return candidate_hit<T, BOXES>(p, i, kind, x, rad, bi, tj, s, defer); },
         overlap);
 }
@@ -316,13 +316,14 @@ template <typename T> struct Lead {
 // the discovery index d = pdidx[u * stride] < WIDE_HPOS (LDS, PM = 2: wide
 // form) or gathered from the step-start snapshot (PM = 0, and PM = 2 past
 // WIDE_HPOS).  A template flag, so LDS accesses stay ds_read (no flat loads).
-template <typename T, int PM, bool BOXES = false, int SDEPTH = 1>
+template <typename T, int PM, bool BOXES = false, int SDEPTH = 1, bool EP = false>
 __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, int32_t i, V3<T> x, int32_t kind,
                                             V3<T> sz, T bi, const BodyIn<T> &in, bool forced, LazyInvI<T> &invI,
                                             int32_t np_, const int32_t *pid, int64_t stride, const Snap<T> *ppos,
                                             int tid, int32_t *cell, uint32_t gen_next, T *poly = nullptr,
                                             int ps = 0, const uint8_t *pdidx = nullptr, int32_t nrec_in = 0,
-                                            bool planes_done = false) {
+                                            bool planes_done = false, const Table<T> *next_tab = nullptr,
+                                            uint32_t keep = NO_BUCKET) {
     const Q4<T> q = in.q;
     V3<T> v = in.v;
     V3<T> w = in.w;
@@ -491,7 +492,11 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     constexpr int L = (PM == 2 || (PM == 0 && !BOXES)) ? LAYOUT_LINEAR : LAYOUT_ANY;
     // heads per line: known in the cooperative and wide forms (rb_capi.hip)
     constexpr int RL = PM == 1 ? 0 : PM == 2 ? 2 : -1;
-    if (p.next.line) cl = claim_slot<L, RL>(p.grid, p.next, p.err, sn, gen_next);
+    // next_tab: the table chosen by the step's epoch control word (step_body);
+    // keep: append steps, the bucket that lists the body already — a body
+    // still in it claims and publishes nothing
+    const Table<T> &next = next_tab ? *next_tab : p.next;
+    if (next.line) cl = claim_slot<L, RL>(p.grid, next, p.err, sn, gen_next, keep);
     wt_store(p.snap_next + i, sn);
     if (p.bounds) {                              // peer-to-peer exchange: this body's new cell
         int32_t cx, cy, cz;
@@ -514,14 +519,27 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
         T *qs = p.quat_next + 4 * (int64_t)i;
         wt_store(qs + 0, qn.w); wt_store(qs + 1, qn.x); wt_store(qs + 2, qn.y); wt_store(qs + 3, qn.z);
     }
-    publish_slot<RL>(p.next, p.err, cl, sn, (uint32_t)i | (kind != 0 ? BOX_FLAG : 0u));
+    publish_slot<RL>(next, p.err, cl, sn, (uint32_t)i | (kind != 0 ? BOX_FLAG : 0u));
+    // worlds with append epochs: a claim past the bucket's head — by an
+    // appender, or by any body of a rebuild step (a pile: the table starts
+    // crowded) — raises the crowding flag; block 0 of the next step reads
+    // it and cuts the epoch short (step_body).  A plain store by one lane
+    // per wave: every writer stores the same word, so no atomic is needed
+    // (a pile raises it from a thousand waves per step)
+    if constexpr (EP) {
+        {
+            const bool past = cl.ok && (uint32_t)(cl.old >> 32) == cl.gen && (uint32_t)cl.old >= (uint32_t)WIDE_HEAD_IDS;
+            const unsigned long long m = __ballot(past);
+            if (past && (int)(threadIdx.x & 63) == __ffsll(m) - 1) *p.ep.crowd = 1;
+        }
+    }
     STAMP(6);
 }
 
 // One body (G lanes): contact search, then (lane 0) the update.  WIDE: the
 // one-lane form for one wave per SIMD (search_buckets_wide; state loads and
 // inv(I_w) under the head loads).
-template <typename T, int MAXP, int G, bool WIDE, bool BOXES, bool PRE = false, bool HELP = false>
+template <typename T, int MAXP, int G, bool WIDE, bool BOXES, bool PRE = false, bool HELP = false, bool EP = false>
 __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> &ld, bool active, int64_t lb, int slot,
                                           int k, int tid,
                                           int32_t *s_id, Snap<T> *s_pos, int32_t *t_id, Snap<T> *t_pos,
@@ -566,8 +584,38 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         asm volatile("" ::"s"(p.grid.inv_cs), "s"(p.grid.H), "s"(p.grid.super), "s"(p.cur.line), "s"(p.cur.gen),
                      "s"(p.n_global), "s"(p.xfrc));
         if constexpr (G > 1) asm volatile("" ::"s"(p.cur.pos));
+        // (the epoch fields too: the bucket head loads wait for the table's
+        // choice, so they belong to the same scalar round trip)
+        if constexpr (EP) asm volatile("" ::"s"(p.ep.ctrl), "s"(p.ep.line[0]), "s"(p.ep.line[1]));
         gen = *p.cur.gen;
     }
+    // append epochs (EP: launches of worlds that run them, launch_step_wide;
+    // rb_internal.hpp Epoch): the control word picks the table this step
+    // reads and the one it inserts into
+    Table<T> cur = p.cur, next = p.next;
+    uint32_t gen_next = gen + 1u;
+    bool ep_append = false;
+    // the table can show appended entries (duplicates, stale ones): it has
+    // been appended to by earlier steps, or this launch's own movers append
+    // to it while other workgroups still read it.  Not in a rebuild step at
+    // age 0: the step before built that table from every body, once each
+    [[maybe_unused]] bool ep_appended = false;
+    if constexpr (EP) {
+        static_assert(PRE && WIDE, "append epochs: the wide step kernels");
+        {
+            const uint32_t cw = *p.ep.ctrl;
+            const uint32_t t = cw & EP_TAB;
+            ep_append = (cw & EP_APPEND) != 0;
+            ep_appended = ep_append || ((cw >> EP_AGE_SHIFT) & 255u) != 0;
+            const uint32_t tn = ep_append ? t : 1u - t;
+            cur.line = t ? p.ep.line[1] : p.ep.line[0];
+            cur.spill = t ? p.ep.spill[1] : p.ep.spill[0];
+            next.line = tn ? p.ep.line[1] : p.ep.line[0];
+            next.spill = tn ? p.ep.spill[1] : p.ep.spill[0];
+            if (ep_append) gen_next = gen;
+        }
+    }
+    [[maybe_unused]] uint32_t b0 = NO_BUCKET;    // the body's step-start bucket (wide search)
     STAMP(1);
     int32_t np_ = 0;
     bool defer = false;                          // a box-involved partner in range: the box kernel steps it
@@ -576,14 +624,14 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         // (help_body); every lane of the body wave takes part in its two
         // barriers, so the search runs under the active mask only
         if (RB_ABLATE != 1 && active)
-            np_ = search_partners_wide<T, MAXP, BOXES>(p, i, kind, x, sz.x, bi, s_id, s_cand, s_didx, s_hpos, tid, gen,
-                                                       defer, [] {});
+            np_ = search_partners_wide<T, MAXP, BOXES, EP>(p, i, kind, x, sz.x, bi, s_id, s_cand, s_didx, s_hpos, tid, gen,
+                                                       cur, ep_appended, b0, defer, [] {});
         __syncthreads();                         // the search is done with s_cand: the helper fills it
         __syncthreads();
     } else if constexpr (G == 1 && WIDE) {
         if (RB_ABLATE != 1)
-            np_ = search_partners_wide<T, MAXP, BOXES>(p, i, kind, x, sz.x, bi, s_id, s_cand, s_didx, s_hpos, tid, gen,
-                                                       defer, [&] {
+            np_ = search_partners_wide<T, MAXP, BOXES, EP>(p, i, kind, x, sz.x, bi, s_id, s_cand, s_didx, s_hpos, tid, gen,
+                                                       cur, ep_appended, b0, defer, [&] {
                 invI.get();
                 if (!p.xfrc) {
                     apply_force(p, l, in.m, invI, in.v, in.w);
@@ -650,10 +698,10 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     }
     constexpr int PM = G > 1 ? 1 : (WIDE && RB_WIDE_LDSPOS) ? 2 : 0;
     constexpr int SD = (WIDE && HELP) ? RB_SOLVE_DEPTH : 1;
-    body_update<T, PM, BOXES, SD>(p, l, i, x, kind, sz, bi, in, forced, invI, np_, s_id + slot, NB,
-                                  PM == 2 ? s_hpos + slot : s_pos + slot, tid, cell, gen + 1u,
+    body_update<T, PM, BOXES, SD, EP>(p, l, i, x, kind, sz, bi, in, forced, invI, np_, s_id + slot, NB,
+                                  PM == 2 ? s_hpos + slot : s_pos + slot, tid, cell, gen_next,
                                   BOXES ? s_poly + slot : nullptr, NB, PM == 2 ? s_didx + slot : nullptr, help_nrec,
-                                  help_planes);
+                                  help_planes, EP ? &next : nullptr, ep_append ? b0 : NO_BUCKET);
 }
 
 // Halo exchange: fold the wave's new cells, given as per-lane boxes
@@ -774,7 +822,8 @@ __device__ __forceinline__ void help_body(const StepParams<T> &p, const Lead<T> 
 // HALO: the halo push compiled in (checked at run time: p.halo.mail); the
 // wide forms — the single-GPU bench's kernels — are also instantiated
 // without it (launch_step_wide picks), which measured 1-2 % faster at C3
-template <typename T, int MAXP, int G, bool WIDE = false, bool BOXES = false, bool HELP = false, bool HALO = true>
+template <typename T, int MAXP, int G, bool WIDE = false, bool BOXES = false, bool HELP = false, bool HALO = true,
+          bool EP = false>
 __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> &ld) {
     constexpr int NB = STEP_BLOCK / G;          // bodies per workgroup
     __shared__ int32_t s_id[MAXP * NB];
@@ -819,7 +868,7 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     const bool active = lb < ld.n_local;
     int32_t cell[6] = {INT32_MAX, 0, 0, 0, 0, 0};   // new cell, step-start cell (peer-to-peer exchange)
     if (G > 1 || HELP || active)                 // (a helper's barriers: every lane)
-        body_step<T, MAXP, G, WIDE, BOXES, true, HELP>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos, s_cand,
+        body_step<T, MAXP, G, WIDE, BOXES, true, HELP, EP>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos, s_cand,
                                                        cell, 0u /* loaded in body_step */, s_poly, s_didx, s_hpos, help_lds);
     if (p.bounds) fold_bounds(p.bounds, cell);
     if (HALO && p.halo.mail) {                   // halo-exchanging shard: push to the peers
@@ -827,7 +876,36 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
         if (halo_bounds(p, halo_e, b)) halo_push(p, halo_e, cell[0] != INT32_MAX, (int32_t)(ld.lo + lb), cell, b);
     }
     if (blockIdx.x == 0 && tid == 0) {
-        if (p.next.line) *p.next.gen = *p.cur.gen + 1u;
+        bool same_gen = false;
+        if constexpr (EP) {
+            {
+                // the next step's control word.  This step's appenders raise
+                // crowd; the flag read here is the one of the step before
+                // (complete), so the schedule is the same in every run.
+                const uint32_t cw = *p.ep.ctrl;
+                const uint32_t t = cw & EP_TAB, age = (cw >> EP_AGE_SHIFT) & 255u, len = (cw >> EP_LEN_SHIFT) & 255u;
+                const uint32_t start = cw >> EP_START_SHIFT;
+                const bool dirty = (cw & EP_DIRTY) || *p.ep.crowd_prev != 0;
+                *p.ep.crowd_prev = 0;
+                uint32_t nw;
+                if (cw & EP_APPEND) {
+                    // crowded: the next step rebuilds
+                    nw = epoch_word(t, age + 1u, dirty ? age + 2u : len, dirty, start);
+                    same_gen = true;
+                    p.ep.count[0] += 1ull;
+                } else {
+                    // a clean epoch doubles the next one's length; a crowded one restarts at 1
+                    // (short epochs while the scene starts up: rb_internal.hpp)
+                    const uint32_t ns = min(start + 1u, 255u);
+                    const uint32_t cap = ns < EP_START_REBUILDS ? min(EP_START_LEN, (uint32_t)p.ep.len_max) : (uint32_t)p.ep.len_max;
+                    const uint32_t nl = dirty ? 1u : min(2u * len, cap);
+                    nw = epoch_word(1u - t, 0u, nl, false, ns);
+                    p.ep.count[1] += 1ull;
+                }
+                *p.ep.ctrl_next = nw;
+            }
+        }
+        if (p.next.line) *p.next.gen = *p.cur.gen + (same_gen ? 0u : 1u);
         if (p.epoch) *p.epoch += 1;
     }
 }
@@ -911,21 +989,21 @@ void box_kernel(StepParams<T> p) {
     if (blockIdx.x == 0 && tid == 0) *p.defer_reset = 0;    // the next step's queue
 }
 // one wave per SIMD (up to 64 x 1024 owned bodies): every register is free
-template <typename T, int MAXP, bool HALO>
+template <typename T, int MAXP, bool HALO, bool EP>
 __global__ __launch_bounds__(STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void step_kernel_wide(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
                       const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, false, HALO>(
+    step_body<T, MAXP, 1, true, false, false, HALO, EP>(
         p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
 }
 
 // the wide form with a helper wave per workgroup (help_body): two waves per
 // SIMD, each within 256 registers
-template <typename T, int MAXP, bool HALO>
+template <typename T, int MAXP, bool HALO, bool EP>
 __global__ __launch_bounds__(2 * STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void step_kernel_wide_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
                            const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, true, HALO>(
+    step_body<T, MAXP, 1, true, false, true, HALO, EP>(
         p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
 }
 
@@ -1259,25 +1337,25 @@ template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int ma
     int64_t blocks = (p.n_local + STEP_BLOCK - 1) / STEP_BLOCK;
     if (blocks < 1) blocks = 1;
     const bool halo = p.halo.mail != nullptr;
-#define RB_WIDE_LAUNCH(K, M, H, TH)                                                                               \
-    hipLaunchKernelGGL((K<T, M, H>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p)
+    // worlds with append epochs (never halo-exchanging: rb_capi.hip
+    // epoch_eligible) launch the instantiation that carries the epoch code
+    const bool ep = p.ep.ctrl != nullptr && !halo;
+#define RB_WIDE_LAUNCH(K, M, H, E, TH)                                                                            \
+    hipLaunchKernelGGL((K<T, M, H, E>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p)
+#define RB_WIDE_PICK(K, M, TH)                                                                                    \
+    do {                                                                                                          \
+        if (halo) RB_WIDE_LAUNCH(K, M, true, false, TH);                                                          \
+        else if (ep) RB_WIDE_LAUNCH(K, M, false, true, TH);                                                       \
+        else RB_WIDE_LAUNCH(K, M, false, false, TH);                                                              \
+    } while (0)
     if (help) {
-        if (maxp <= 16) {
-            if (halo) RB_WIDE_LAUNCH(step_kernel_wide_help, 16, true, 2 * STEP_BLOCK);
-            else RB_WIDE_LAUNCH(step_kernel_wide_help, 16, false, 2 * STEP_BLOCK);
-        } else {
-            if (halo) RB_WIDE_LAUNCH(step_kernel_wide_help, 32, true, 2 * STEP_BLOCK);
-            else RB_WIDE_LAUNCH(step_kernel_wide_help, 32, false, 2 * STEP_BLOCK);
-        }
+        if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide_help, 16, 2 * STEP_BLOCK);
+        else RB_WIDE_PICK(step_kernel_wide_help, 32, 2 * STEP_BLOCK);
         return hipGetLastError();
     }
-    if (maxp <= 16) {
-        if (halo) RB_WIDE_LAUNCH(step_kernel_wide, 16, true, STEP_BLOCK);
-        else RB_WIDE_LAUNCH(step_kernel_wide, 16, false, STEP_BLOCK);
-    } else {
-        if (halo) RB_WIDE_LAUNCH(step_kernel_wide, 32, true, STEP_BLOCK);
-        else RB_WIDE_LAUNCH(step_kernel_wide, 32, false, STEP_BLOCK);
-    }
+    if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide, 16, STEP_BLOCK);
+    else RB_WIDE_PICK(step_kernel_wide, 32, STEP_BLOCK);
+#undef RB_WIDE_PICK
 #undef RB_WIDE_LAUNCH
     return hipGetLastError();
 }
