@@ -1,0 +1,346 @@
+// rb_api_batch.hip — batched worlds (rb_batch_*; kernels in rb_batch.hip).
+// E replicas of a template environment of M <= 64 bodies, body b of
+// environment e at slot e * M + b of every device row.  All work is enqueued
+// on the batch's own stream; every entry point returns after it finished.
+#include "rb_host.hpp"
+
+using namespace rb::host;
+
+static_assert(BATCH_EDOM == RB_EDOM && BATCH_CHUNK == RB_BATCH_CHUNK, "batch constants");
+
+struct rb_batch {
+    int dtype = RB_F64, esz = 8, device = 0;
+    hipStream_t stream = nullptr;
+    int64_t E = 0, N = 0;              // environments, body slots (E * M)
+    int32_t M = 0, n_planes = 0, oriented = 1;
+    bool box = false;                  // the template is one box
+    std::vector<int32_t> kind;         // [M] the template's kinds
+    double planes[RB_MAX_PLANES][6] = {};
+    double g[3] = {};
+    double inv_cs = 1.0;
+    void *snap = nullptr, *state = nullptr, *consts = nullptr;
+    void *env_e = nullptr, *env_mu = nullptr;   // [E] reals; used while have_*
+    bool have_e = false, have_mu = false;
+    int32_t *code = nullptr, *count = nullptr;
+    int64_t *steps_done = nullptr;
+    double *io_q = nullptr, *io_v = nullptr;    // device staging of the AoS rows
+    int64_t io_rows = 0;
+    int64_t *ids = nullptr;                     // device copy of an env_ids list
+    int64_t ids_cap = 0;
+};
+
+namespace {
+
+void free_batch(rb_batch *b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
+                    b->io_q, b->io_v, b->ids};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int bput(rb_batch *b, void *dst, const void *src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RB_OK;
+}
+
+double batch_bound_of(int32_t kind, const double *s) {
+    return kind == RB_BODY_SPHERE ? s[0] : sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+}
+
+// the cell size of a world of these bodies (upload_consts): the position
+// check of a step uses the same predicate
+void batch_set_rmax(rb_batch *b, double rmax) { b->inv_cs = 1.0 / (rmax > 0 ? 4.0 * rmax * 1.001 : 1.0); }
+
+// row r (of the 8 constant rows) <- src[slot * stride + off], as the batch's real type
+int batch_put_row(rb_batch *b, int row, const double *src, int stride, int off) {
+    return by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        std::vector<T> h((size_t)b->N);
+        for (int64_t g = 0; g < b->N; ++g) h[(size_t)g] = (T)src[(size_t)g * stride + off];
+        return bput(b, dp<T>(b->consts, row * b->N), h.data(), sizeof(T) * h.size());
+    });
+}
+
+template <typename T> StateIO<T> batch_io(rb_batch *b) {
+    StateIO<T> p{};
+    p.qpos = b->io_q;
+    p.qvel = b->io_v;
+    p.snap = dp<Snap<T>>(b->snap, 0);
+    p.quat = nullptr;
+    p.st = BodyState<T>{dp<T>(b->state, 0), b->N};
+    p.bound = dp<T>(b->consts, 7 * b->N);
+    p.N = b->N;
+    p.lo = 0;
+    p.n_local = (int32_t)b->N;
+    p.balls = 0;
+    return p;
+}
+
+template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double dt, double e, double mu, double thr) {
+    BatchParams<T> p{};
+    p.snap = dp<Snap<T>>(b->snap, 0);
+    p.st = BodyState<T>{dp<T>(b->state, 0), b->N};
+    p.cs = BodyConsts<T>{dp<T>(b->consts, 0), b->N, nullptr};
+    p.env_e = b->have_e ? dp<T>(b->env_e, 0) : nullptr;
+    p.env_mu = b->have_mu ? dp<T>(b->env_mu, 0) : nullptr;
+    p.code = b->code;
+    p.steps_done = b->steps_done;
+    p.E = b->E;
+    p.M = b->M;
+    p.k = k;
+    p.n_planes = b->n_planes;
+    p.oriented = b->oriented;
+    for (int pl = 0; pl < b->n_planes; ++pl)
+        for (int d = 0; d < 3; ++d) { p.pn[pl][d] = (T)b->planes[pl][d]; p.pp[pl][d] = (T)b->planes[pl][3 + d]; }
+    for (int d = 0; d < 3; ++d) p.g[d] = (T)b->g[d];
+    p.dt = (T)dt; p.e = (T)e; p.mu = (T)mu; p.thr = (T)thr;
+    p.inv_cs = (T)b->inv_cs;
+    return p;
+}
+
+// the listed environments' rows: staging of n * M rows and the ids on the device
+int batch_stage(rb_batch *b, const int64_t *env_ids, int64_t n) {
+    const int64_t rows = n * b->M;
+    if (rows > b->io_rows) {
+        if (b->io_q) { HIPCHK(hipFree(b->io_q)); b->io_q = nullptr; }
+        if (b->io_v) { HIPCHK(hipFree(b->io_v)); b->io_v = nullptr; }
+        b->io_rows = 0;
+        HIPCHK(hipMalloc((void **)&b->io_q, sizeof(double) * 7 * (size_t)rows));
+        HIPCHK(hipMalloc((void **)&b->io_v, sizeof(double) * 6 * (size_t)rows));
+        b->io_rows = rows;
+    }
+    if (env_ids) {
+        if (n > b->ids_cap) {
+            if (b->ids) { HIPCHK(hipFree(b->ids)); b->ids = nullptr; }
+            b->ids_cap = 0;
+            HIPCHK(hipMalloc((void **)&b->ids, sizeof(int64_t) * (size_t)n));
+            b->ids_cap = n;
+        }
+        HIPCHK(hipMemcpyAsync(b->ids, env_ids, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, b->stream));
+    }
+    return RB_OK;
+}
+
+// env_ids == NULL: all environments (n must be n_envs); else n distinct ids in range
+int batch_check_ids(const rb_batch *b, const int64_t *env_ids, int64_t n) {
+    if (!env_ids) return n == b->E ? RB_OK : fail(RB_EINVAL, "env_ids NULL: n must be n_envs (%lld)", (long long)b->E);
+    if (n < 0) return fail(RB_EINVAL, "n < 0");
+    for (int64_t k = 0; k < n; ++k)
+        if (env_ids[k] < 0 || env_ids[k] >= b->E)
+            return fail(RB_EINVAL, "env_ids[%lld] = %lld outside [0, %lld)", (long long)k, (long long)env_ids[k], (long long)b->E);
+    return RB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
+    ApiScope api_scope_(d ? d->device : -1);
+    if (!out || !d) return fail(RB_EINVAL, "null argument");
+    *out = nullptr;
+    if (n_envs < 1) return fail(RB_EINVAL, "n_envs must be >= 1");
+    if (d->n_bodies < 1 || d->n_bodies > 64) return fail(RB_EINVAL, "n_bodies (bodies per environment) must be in [1, 64]");
+    if (d->world_size != 1 || d->rank != 0) return fail(RB_EINVAL, "a batch is not sharded: world_size must be 1, rank 0");
+    if (n_envs > ((int64_t)INT32_MAX / 2) / d->n_bodies) return fail(RB_EINVAL, "n_envs * n_bodies out of range");
+    if (d->n_planes < 0 || d->n_planes > RB_MAX_PLANES) return fail(RB_EINVAL, "n_planes must be in [0, %d]", RB_MAX_PLANES);
+    if (d->dtype != RB_F64 && d->dtype != RB_F32) return fail(RB_EINVAL, "dtype must be RB_F64 or RB_F32");
+    if (!d->kind || !d->mass || !d->inertia || !d->size || (d->n_planes && !d->planes))
+        return fail(RB_EINVAL, "null scene array");
+    if (d->normal_convention != RB_NORMAL_ORIENTED && d->normal_convention != RB_NORMAL_RAW)
+        return fail(RB_EINVAL, "bad normal_convention");
+    bool any_box = false;
+    for (int64_t k = 0; k < d->n_bodies; ++k) {
+        if (d->kind[k] != RB_BODY_SPHERE && d->kind[k] != RB_BODY_BOX) return fail(RB_EINVAL, "body %lld: bad kind", (long long)k);
+        if (!(d->mass[k] > 0)) return fail(RB_EINVAL, "body %lld: mass must be > 0", (long long)k);
+        any_box = any_box || d->kind[k] == RB_BODY_BOX;
+    }
+    if (any_box && d->n_bodies > 1)
+        return fail(RB_EUNSUPPORTED, "rb_batch: unsupported template: a box body in an environment of more than one body "
+                                     "(box-involved pairs are stepped by rb_world)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RB_ENODEV, "no HIP device available");
+    if (d->device < 0 || d->device >= ndev) return fail(RB_ENODEV, "device %d out of range (have %d)", d->device, ndev);
+
+    rb_batch *b = new rb_batch();
+    b->dtype = d->dtype;
+    b->esz = d->dtype == RB_F64 ? 8 : 4;
+    b->device = d->device;
+    b->E = n_envs;
+    b->M = (int32_t)d->n_bodies;
+    b->N = b->E * b->M;
+    b->box = any_box;
+    b->kind.assign(d->kind, d->kind + d->n_bodies);
+    b->n_planes = d->n_planes;
+    for (int k = 0; k < d->n_planes; ++k)
+        for (int j = 0; j < 6; ++j) b->planes[k][j] = d->planes[6 * k + j];
+    for (int j = 0; j < 3; ++j) b->g[j] = d->gravity[j];
+    b->oriented = d->normal_convention == RB_NORMAL_ORIENTED;
+    auto bail = [&](int rc) { free_batch(b); return rc; };
+    if (hipSetDevice(b->device) != hipSuccess) return bail(fail(RB_ENODEV, "hipSetDevice(%d) failed", b->device));
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(fail(RB_ENODEV, "hipStreamCreate failed"));
+    const size_t esz = (size_t)b->esz, N = (size_t)b->N, E = (size_t)b->E;
+    const std::pair<void **, size_t> allocs[] = {
+        {&b->snap, esz * 4 * N}, {&b->state, esz * 13 * N}, {&b->consts, esz * 8 * N},
+        {&b->env_e, esz * E}, {&b->env_mu, esz * E}, {(void **)&b->code, sizeof(int32_t) * E},
+        {(void **)&b->count, sizeof(int32_t)}, {(void **)&b->steps_done, sizeof(int64_t) * E}};
+    for (const auto &a : allocs) {
+        if (hipMalloc(a.first, a.second) != hipSuccess) return bail(fail(RB_ENOMEM, "hipMalloc(%zu) failed", a.second));
+        if (hipMemsetAsync(*a.first, 0, a.second, b->stream) != hipSuccess) return bail(fail(RB_ENODEV, "hipMemsetAsync failed"));
+    }
+    // the template's constants, replicated per environment
+    std::vector<double> mass(N), inertia(3 * N), size(3 * N);
+    for (size_t g = 0; g < N; ++g) {
+        const size_t k = g % (size_t)b->M;
+        mass[g] = d->mass[k];
+        for (int j = 0; j < 3; ++j) { inertia[3 * g + j] = d->inertia[3 * k + j]; size[3 * g + j] = d->size[3 * k + j]; }
+    }
+    if (int rc = rb_batch_set_bodies(b, mass.data(), inertia.data(), size.data())) return bail(rc);
+    *out = b;
+    return RB_OK;
+}
+
+void rb_batch_destroy(rb_batch *b) {
+    ApiScope api_scope_(b ? b->device : -1);
+    free_batch(b);
+}
+
+int rb_batch_set_params(rb_batch *b, const double *restitution, const double *friction) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    for (int64_t e = 0; e < b->E; ++e)
+        if ((restitution && !(restitution[e] >= 0)) || (friction && !(friction[e] >= 0)))
+            return fail(RB_EINVAL, "environment %lld: restitution and friction must be >= 0", (long long)e);
+    HIPCHK(hipSetDevice(b->device));
+    const double *src[2] = {restitution, friction};
+    void *dst[2] = {b->env_e, b->env_mu};
+    for (int k = 0; k < 2; ++k) {
+        if (!src[k]) continue;
+        WCHK(by_real(b->dtype, [&](auto t) {
+            const std::vector<decltype(t)> f(src[k], src[k] + b->E);
+            return bput(b, dst[k], f.data(), sizeof(f[0]) * f.size());
+        }));
+    }
+    b->have_e = restitution != nullptr;
+    b->have_mu = friction != nullptr;
+    return RB_OK;
+}
+
+int rb_batch_set_bodies(rb_batch *b, const double *mass, const double *inertia, const double *size) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (mass)
+        for (int64_t g = 0; g < b->N; ++g)
+            if (!(mass[g] > 0)) return fail(RB_EINVAL, "body slot %lld: mass must be > 0", (long long)g);
+    HIPCHK(hipSetDevice(b->device));
+    if (mass) WCHK(batch_put_row(b, 0, mass, 1, 0));
+    if (inertia)
+        for (int j = 0; j < 3; ++j) WCHK(batch_put_row(b, 1 + j, inertia, 3, j));
+    if (size) {
+        for (int j = 0; j < 3; ++j) WCHK(batch_put_row(b, 4 + j, size, 3, j));
+        std::vector<double> bound((size_t)b->N);
+        double rmax = 0;
+        for (int64_t g = 0; g < b->N; ++g) {
+            bound[(size_t)g] = batch_bound_of(b->kind[(size_t)(g % b->M)], size + 3 * g);
+            if (bound[(size_t)g] > rmax) rmax = bound[(size_t)g];
+        }
+        WCHK(batch_put_row(b, 7, bound.data(), 1, 0));
+        batch_set_rmax(b, rmax);
+        // the snapshots carry the bounding radius
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_batch_bound<T>(dp<Snap<T>>(b->snap, 0), dp<T>(b->consts, 7 * b->N), b->N, b->stream);
+        }));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return RB_OK;
+}
+
+int rb_batch_set_state(rb_batch *b, const int64_t *env_ids, int64_t n, const double *qpos, const double *qvel) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b || !qpos || !qvel) return fail(RB_EINVAL, "null argument");
+    WCHK(batch_check_ids(b, env_ids, n));
+    if (n == 0) return RB_OK;
+    HIPCHK(hipSetDevice(b->device));
+    WCHK(batch_stage(b, env_ids, n));
+    const size_t rows = (size_t)(n * b->M);
+    HIPCHK(hipMemcpyAsync(b->io_q, qpos, sizeof(double) * 7 * rows, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->io_v, qvel, sizeof(double) * 6 * rows, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return env_ids ? launch_batch_state_in<T>(batch_io<T>(b), b->ids, n, b->M, b->stream)
+                       : launch_state_in<T>(batch_io<T>(b), b->stream);
+    }));
+    HIPCHK(launch_batch_reset(b->code, b->steps_done, env_ids ? b->ids : nullptr, n, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RB_OK;
+}
+
+int rb_batch_get_state(rb_batch *b, const int64_t *env_ids, int64_t n, double *qpos, double *qvel) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b || (!qpos && !qvel)) return fail(RB_EINVAL, "null argument");
+    WCHK(batch_check_ids(b, env_ids, n));
+    if (n == 0) return RB_OK;
+    HIPCHK(hipSetDevice(b->device));
+    WCHK(batch_stage(b, env_ids, n));
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return env_ids ? launch_batch_state_out<T>(batch_io<T>(b), b->ids, n, b->M, b->stream)
+                       : launch_state_out<T>(batch_io<T>(b), true, true, b->stream);
+    }));
+    const size_t rows = (size_t)(n * b->M);
+    if (qpos) HIPCHK(hipMemcpyAsync(qpos, b->io_q, sizeof(double) * 7 * rows, hipMemcpyDeviceToHost, b->stream));
+    if (qvel) HIPCHK(hipMemcpyAsync(qvel, b->io_v, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RB_OK;
+}
+
+int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr, int64_t *n_failed) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (nsteps < 0) return fail(RB_EINVAL, "nsteps < 0");
+    if (!(dt > 0) || !(e >= 0) || !(mu >= 0) || !(thr >= 0))
+        return fail(RB_EINVAL, "invalid step parameters dt=%g e=%g mu=%g thr=%g", dt, e, mu, thr);
+    HIPCHK(hipSetDevice(b->device));
+    // launches of at most RB_BATCH_CHUNK steps: the state between two of them
+    // is the state between two steps, so the cut changes nothing
+    for (int64_t left = nsteps; left > 0; left -= BATCH_CHUNK) {
+        const int32_t k = (int32_t)std::min<int64_t>(left, BATCH_CHUNK);
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_batch_step<T>(batch_params<T>(b, k, dt, e, mu, thr), b->box, b->stream);
+        }));
+    }
+    int32_t cnt = 0;
+    HIPCHK(hipMemsetAsync(b->count, 0, sizeof(int32_t), b->stream));
+    HIPCHK(launch_batch_count(b->code, b->E, b->count, b->stream));
+    HIPCHK(hipMemcpyAsync(&cnt, b->count, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (n_failed) {
+        *n_failed = cnt;
+        return RB_OK;
+    }
+    if (cnt > 0)
+        return fail(RB_EDOM, "device: non-finite or out-of-range body position in %d environment(s) (rb_batch_status)", cnt);
+    return RB_OK;
+}
+
+int rb_batch_status(rb_batch *b, int32_t *code, int64_t *steps_done) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b || (!code && !steps_done)) return fail(RB_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(b->device));
+    if (code) HIPCHK(hipMemcpyAsync(code, b->code, sizeof(int32_t) * (size_t)b->E, hipMemcpyDeviceToHost, b->stream));
+    if (steps_done)
+        HIPCHK(hipMemcpyAsync(steps_done, b->steps_done, sizeof(int64_t) * (size_t)b->E, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RB_OK;
+}
+
+}  // extern "C"

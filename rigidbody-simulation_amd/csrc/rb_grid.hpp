@@ -119,7 +119,7 @@ __device__ __forceinline__ uint32_t bucket_linear(int32_t ix, int32_t iy, int32_
     return (sc << gb) | in;
 }
 // Layouts a kernel may assume at compile time: LAYOUT_LINEAR in the one-lane
-// and wide forms (their worlds always use it: rb_capi.hip), LAYOUT_ANY
+// and wide forms (their worlds always use it: rb_api_world.hip), LAYOUT_ANY
 // reads Grid::super
 enum : int { LAYOUT_ANY = 0, LAYOUT_LINEAR = 1 };
 template <int L = LAYOUT_ANY, typename T>
@@ -603,7 +603,7 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
     int32_t c[8];
     Head6 hd[8];
     neighbour_buckets<LAYOUT_LINEAR>(p.grid, cx, cy, cz, sx, sy, sz, b);
-    constexpr int rl = 2;                         // heads per line: wide-form worlds 4 (rb_capi.hip)
+    constexpr int rl = 2;                         // heads per line: wide-form worlds 4 (rb_api_world.hip)
 #pragma unroll
     for (int k = 0; k < 8; ++k) hd[k] = bucket_head6(cur, (uint32_t)CHK(b[k], p.grid.H), rl);
     b0 = b[0];                                    // the body's own bucket

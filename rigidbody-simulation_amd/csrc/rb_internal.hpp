@@ -1,5 +1,5 @@
 // rb_internal.hpp — shared between the kernels (rb_kernels.hip) and the
-// C-ABI implementation (rb_capi.hip).  Not part of the public interface.
+// C-ABI implementation (rb_api_*.hip, which share rb_host.hpp).  Not part of the public interface.
 #pragma once
 
 #include <cstddef>

@@ -156,7 +156,7 @@ __device__ __forceinline__ int32_t search_coop(const StepParams<T> &p, bool acti
     // loaded unconditionally (b is a valid bucket for every lane) and the
     // count clamped only after overlap(): a use inside a branch would make
     // the wave wait for the loads before that work starts
-    const int rl = RL >= 0 ? RL : grid_rl(p.grid.super);   // heads per line: cooperative worlds 1 (rb_capi.hip)
+    const int rl = RL >= 0 ? RL : grid_rl(p.grid.super);   // heads per line: cooperative worlds 1 (rb_api_world.hip)
     const uint4 id4 = bucket_head(p.cur, b, rl);
     Snap<T> p4[QS > 0 ? QS : 1];                  // (RB_QSPEC=0: a diagnostic build)
 #pragma unroll
@@ -490,7 +490,7 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     // linear-layout worlds only; the cooperative form and the box kernel
     // read the layout
     constexpr int L = (PM == 2 || (PM == 0 && !BOXES)) ? LAYOUT_LINEAR : LAYOUT_ANY;
-    // heads per line: known in the cooperative and wide forms (rb_capi.hip)
+    // heads per line: known in the cooperative and wide forms (rb_api_world.hip)
     constexpr int RL = PM == 1 ? 0 : PM == 2 ? 2 : -1;
     // next_tab: the table chosen by the step's epoch control word (step_body);
     // keep: append steps, the bucket that lists the body already — a body
@@ -660,7 +660,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     if (RB_ABLATE == 7) np_ = 0;                 // diagnostic: search, but solve no partner contact
     if (!active || k != 0 || RB_ABLATE == 4) return;
     if (!BOXES && defer) {                       // box worlds only (p.defer_q set)
-        // queued for the box kernel; chunks replayed without it (rb_capi.hip
+        // queued for the box kernel; chunks replayed without it (rb_api_step.hip
         // box_opt) only count, and are rolled back if the count is not zero
         const int32_t q = atomicAdd(p.defer_cnt, 1);
         if (q < p.S) p.defer_q[q] = l;
@@ -1213,7 +1213,7 @@ template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, i
 // ---- the state across the boundary (rb_set_state / rb_get_state) ----------
 // One lane per body: AoS rows of the caller (qpos[7k], qvel[6k], D1-fixed
 // multi_sphere_bounce.py layout) <-> SoA state rows and snapshot.  The host
-// moves the rows with one DMA each way (pinned staging, rb_capi.hip).
+// moves the rows with one DMA each way (pinned staging, rb_api_state.hip).
 template <typename T>
 __global__ __launch_bounds__(256) void state_in_kernel(StateIO<T> p) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1337,7 +1337,7 @@ template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int ma
     int64_t blocks = (p.n_local + STEP_BLOCK - 1) / STEP_BLOCK;
     if (blocks < 1) blocks = 1;
     const bool halo = p.halo.mail != nullptr;
-    // worlds with append epochs (never halo-exchanging: rb_capi.hip
+    // worlds with append epochs (never halo-exchanging: rb_api_step.hip
     // epoch_eligible) launch the instantiation that carries the epoch code
     const bool ep = p.ep.ctrl != nullptr && !halo;
 #define RB_WIDE_LAUNCH(K, M, H, E, TH)                                                                            \

@@ -17,9 +17,8 @@ os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
 for k, v in enumerate(variants if not os.environ.get("LIBS") else []):
     out = os.path.join(ROOT, "build", f"ablate{k}.so")
     if os.environ.get("PREBUILT") != "1":
-        subprocess.run(f"/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off "
-                       f"{v} -o {out} rb_kernels.hip rb_balls.hip rb_p2p.hip rb_capi.hip", shell=True,
-                       check=True, cwd=CSRC)
+        # the product's Makefile (its units and flags) with the variant's flags on every unit
+        subprocess.run(["make", "-s", "-C", CSRC, f"EXTRA={v}", f"OUT={out}", f"OBJDIR=build/ablate{k}"], check=True)
     paths[v] = out
 if os.environ.get("BUILD_ONLY") == "1":
     sys.exit(0)

@@ -1,5 +1,5 @@
 """Diagnostic (CPU, oracle): the world's linear bucket layout under drift.
-The layout's period split (rb_capi.hip fit_period: lg bits over x, y, z,
+The layout's period split (rb_api_state.hip fit_period: lg bits over x, y, z,
 scored by colliding groups) is fitted to the positions at rb_set_state.
 Here: the split chosen at t = 0 for C4, and at later steps the ids a body's
 eight buckets hold under that split (aliased cells included) against the

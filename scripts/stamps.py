@@ -11,9 +11,8 @@ extra = os.environ.get("EXTRA_FLAGS", "")
 # a prebuilt stamps library (built on the CPU host, shipped with the tree) or build one here
 LIB = os.environ.get("STAMP_LIB", "/tmp/libstamp.so")
 if not os.path.exists(LIB):
-    subprocess.run(f"/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off "
-                   f"-DRB_STAMPS=1 {extra} -o {LIB} rb_kernels.hip rb_balls.hip rb_p2p.hip rb_capi.hip", shell=True,
-                   check=True, cwd=CSRC)
+    subprocess.run(["make", "-s", "-C", CSRC, f"EXTRA=-DRB_STAMPS=1 {extra}".strip(), f"OUT={LIB}", "OBJDIR=build/stamps"],
+                   check=True)
 from rbhip import _lib, scenes
 import rbhip.world as W
 L = _lib.load(LIB)

@@ -1,6 +1,6 @@
 """Diagnostic: per-phase cycle stamps of the step kernel in C4's pile-up
 phase (RB_STAMPS build, e.g. `make -C rigidbody-simulation_amd/csrc
-OUT=../../build/stamps.so OBJDIR=build_stamps EXTRA=-DRB_STAMPS=1`).
+OUT=../../build/stamps.so OBJDIR=build/stamps EXTRA=-DRB_STAMPS=1`).
 C4 (65,536 spheres on the incline) is stepped from t = 0 to `--warm` steps
 (max_partners 32, the bench's c4 world), then one recorded launch; prints
 the phase spans of the slowest blocks and the median, and how many blocks

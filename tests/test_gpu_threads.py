@@ -49,7 +49,7 @@ def test_two_threads_each_with_own_worlds(rb_lib=None):
 
 
 def test_threads_on_two_devices_capture_while_the_other_allocates(rb_lib=None):
-    """The capture gate serialises per device (rb_capi.hip ApiScope /
+    """The capture gate serialises per device (rb_api_common.hip ApiScope /
     CaptureScope): a thread replaying captured step graphs on device 0 while
     another creates, steps and destroys worlds (hipMalloc, fills, captures)
     on device 1 must see no failed capture and exact results on both.
