@@ -281,6 +281,77 @@ def crowded_cells(nx: int = 10, ny: int = 10, layers: int = 4, seed: int = 0) ->
                  dt=0.005, restitution=0.3, friction=0.4, threshold=0.0)
 
 
+def _trough_planes(a: float) -> np.ndarray:
+    """A V trough along y: two planes through the origin tilted +-a about y."""
+    return np.array([[np.sin(a), 0.0, np.cos(a), 0.0, 0.0, 0.0],
+                     [-np.sin(a), 0.0, np.cos(a), 0.0, 0.0, 0.0]])
+
+
+def _unit_quats(rng, n):
+    q = rng.standard_normal((n, 4))
+    return q / np.linalg.norm(q, axis=1)[:, None]
+
+
+def mixed_spheres(nx: int, ny: int, seed: int = 0, spacing: float = 0.3, types=None) -> Scene:
+    """Heterogeneous spheres (no reference counterpart): an nx*ny grid, every
+    body with its own radius U(0.06, 0.12) (cells are 4 r_max: ratio <= 2),
+    mass U(0.1, 2.0) and anisotropic inertia U(1e-3, 5e-3) per axis — or,
+    with types=k, one of k such (m, I) rows per body — and a random unit
+    quaternion; z = U(0.3, 1.2) + 0.35 |x|, v_xy ~ N(0, 0.3^2), w ~ N(0, 2^2).
+    Three planes: a V trough (+-0.3 rad about y, through the origin) and a
+    wall y >= -(ny*spacing/2 + 0.2); gravity tilted to (0.3, -0.2, -9.8) so
+    the bodies run into the wall; e 0.6, mu 0.4, dt 0.01, threshold 1e-4."""
+    n = nx * ny
+    rng = np.random.default_rng(seed)
+    iy, ix = np.divmod(np.arange(n), nx)
+    qpos = np.zeros((n, 7))
+    qpos[:, 0] = (ix - (nx - 1) / 2.0) * spacing
+    qpos[:, 1] = (iy - (ny - 1) / 2.0) * spacing
+    size = np.zeros((n, 3))
+    size[:, 0] = rng.uniform(0.06, 0.12, n)
+    if types is None:
+        mass = rng.uniform(0.1, 2.0, n)
+        inertia = rng.uniform(1e-3, 5e-3, (n, 3))
+    else:
+        rows_m = rng.uniform(0.1, 2.0, types)
+        rows_i = rng.uniform(1e-3, 5e-3, (types, 3))
+        t = rng.integers(0, types, n)
+        mass, inertia = rows_m[t], rows_i[t]
+    qpos[:, 2] = rng.uniform(0.3, 1.2, n) + 0.35 * np.abs(qpos[:, 0])
+    qpos[:, 3:7] = _unit_quats(rng, n)
+    qvel = np.zeros((n, 6))
+    qvel[:, 0:2] = rng.normal(0.0, 0.3, (n, 2))
+    qvel[:, 3:6] = rng.normal(0.0, 2.0, (n, 3))
+    planes = np.concatenate([_trough_planes(0.3),
+                             [[0.0, 1.0, 0.0, 0.0, -(ny * spacing / 2.0 + 0.2), 0.0]]])
+    return Scene(f"mixed_spheres_{n}", np.full(n, SPHERE, np.int32), mass, inertia, size, planes, qpos, qvel,
+                 dt=0.01, restitution=0.6, friction=0.4, threshold=1e-4,
+                 gravity=np.array([0.3, -0.2, -9.8]))
+
+
+def trough_bricks(n: int, seed: int = 0) -> Scene:
+    """Non-cubic boxes on two planes at once (no reference counterpart): n
+    bricks in a row along y, 3.0 apart (> 2*sqrt(3)*0.45: no brick-brick
+    contact), x ~ U(-0.3, 0.3), z ~ U(0.9, 1.3), random unit quaternions,
+    w ~ N(0, 1), dropped into a V trough of +-0.4 rad about y; half extents
+    U(0.15, 0.45) per axis, mass U(5, 30), inertia U(0.5, 3.0) per axis;
+    gravity (0, 0.1, -9.8); e 0.2, mu 0.6, dt 0.009, threshold 1e-4."""
+    rng = np.random.default_rng(seed)
+    qpos = np.zeros((n, 7))
+    qpos[:, 0] = rng.uniform(-0.3, 0.3, n)
+    qpos[:, 1] = (np.arange(n) - (n - 1) / 2.0) * 3.0
+    qpos[:, 2] = rng.uniform(0.9, 1.3, n)
+    qpos[:, 3:7] = _unit_quats(rng, n)
+    qvel = np.zeros((n, 6))
+    qvel[:, 3:6] = rng.normal(0.0, 1.0, (n, 3))
+    size = rng.uniform(0.15, 0.45, (n, 3))
+    mass = rng.uniform(5.0, 30.0, n)
+    inertia = rng.uniform(0.5, 3.0, (n, 3))
+    return Scene(f"trough_bricks_{n}", np.full(n, BOX, np.int32), mass, inertia, size, _trough_planes(0.4),
+                 qpos, qvel, dt=0.009, restitution=0.2, friction=0.6, threshold=1e-4,
+                 gravity=np.array([0.0, 0.1, -9.8]))
+
+
 CONFIGS = {
     # BASELINE.json configs, in order
     "c1": single_sphere,

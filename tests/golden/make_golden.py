@@ -562,6 +562,10 @@ def main():
         ("traj_flat256", scenes.flat_spheres(16, 16, seed=2), 150, 10, 150),
         ("traj_incline64", scenes.incline_spheres(8, 8, seed=3), 200, 10, 200),
         ("traj_cubes16", scenes.incline_cubes(4, 4, seed=4), 240, 10, 240),
+        # heterogeneous bodies, several planes, tilted gravity, threshold 1e-4
+        ("traj_mixed48", scenes.mixed_spheres(8, 6, seed=1), 200, 10, 200),
+        ("traj_mixed48_raw", scenes.mixed_spheres(8, 6, seed=1).with_(normal_convention="raw"), 200, 10, 200),
+        ("traj_bricks6", scenes.trough_bricks(6, seed=2), 300, 10, 300),
     ]
     for name, sc, steps, every, csteps in nb:
         if want(name):
