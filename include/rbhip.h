@@ -335,11 +335,12 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * replicas of a template environment of M = n_bodies <= 64 bodies; planes,
  * gravity, dt, the contact threshold and the normal convention are per
  * batch, restitution / friction / body constants / state per environment.
- * An environment steps bit-identically to an rb_world of the same scene.
+ * An environment steps bit-identically to an rb_world of the same scene,
+ * under either contact law (rb_batch_set_contact_law).
  * Arrays are environment-major: body k of environment e at row e*M + k.
  * Not covered (use rb_world): applied forces, contact recording, caller
  * streams and asynchronous stepping, sharding, box-involved pairs (a box is
- * accepted only as the single body of its environment), the two-ball law,
+ * accepted only as the single body of its environment),
  * per-environment planes or gravity, more than 64 bodies per environment.
  * A batch handle is not thread-safe; every call is synchronous.
  *
@@ -388,6 +389,47 @@ int  rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double restitution, d
  * the environment's last rb_batch_set_state); either may be NULL.  No
  * reference counterpart (the reference raises from inside its one scene). */
 int  rb_batch_status(rb_batch *b, int32_t *code, int64_t *steps_done);
+/* Switch a batch to RB_LAW_BALLS (or back to RB_LAW_MUJOCO): every
+ * environment then steps as step_with_custom_collisions
+ * (ball_collision.py:73-125) with compute_collision_impulse
+ * (ball_collision.py:53-68), exactly as rb_set_contact_law describes it for a
+ * world; an environment of N > 2 balls evaluates every pair (a < b) from the
+ * post-ground state of both and accumulates per ball in ascending partner id
+ * (no partner cap: every ball may touch all others).  Same conditions and
+ * codes as rb_set_contact_law: spheres only and either no plane or exactly
+ * the z = 0 ground plane, else RB_EUNSUPPORTED; tol finite and >= 0 (the
+ * reference: 0.01, ball_collision.py:102) and a known law, else RB_EINVAL; a
+ * refused call changes nothing.  Under RB_LAW_BALLS the contact_threshold of
+ * rb_batch_step is ignored, and so are the inertia rows of
+ * rb_batch_set_bodies: the law derives I^-1 from mass and radius
+ * (compute_inverse_inertia, ball_collision.py:39-41).  Per-environment
+ * restitution / friction (rb_batch_set_params) apply to the ground and the
+ * pair impulses.  The law may be switched between calls: the quaternion is
+ * never touched under RB_LAW_BALLS and no state is converted. */
+int  rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol);
+/* rb_batch_step that also records the curves the reference logs while it
+ * steps (logger_base.py, data_logger.py, multi_sphere_logger.py: height
+ * against time and the 3-D trajectory of every run): after every every-th step
+ * of this call the state of every body of every environment, S = nsteps /
+ * every samples (rounded down; the steps after the last sample are still
+ * run).  Sample s is the state after step (s + 1) * every of this call, at
+ * qpos [S][n_envs][M][7] and qvel [S][n_envs][M][6] (host arrays of the
+ * caller; qvel NULL: positions and quaternions only) — word for word what a
+ * loop of rb_batch_step(every) + rb_batch_get_state(all) returns, a failed
+ * environment's rows repeating its frozen state; final state, status and
+ * steps_done are those of rb_batch_step(nsteps).  The samples are taken
+ * inside the step kernel's register loop (launches still run at most
+ * RB_BATCH_CHUNK steps, the sampling period running on across them) into a
+ * device buffer owned by the batch, allocated on first use, of at most
+ * RBHIP_BATCH_SAMPLE_BYTES bytes (environment variable read by
+ * rb_batch_create; default 256 MiB); one sample takes n_envs * M * rows *
+ * (sizeof(real) + 8) bytes, rows = 13, or 7 without qvel.  A run whose
+ * samples do not fit is cut into shorter launches with the buffer downloaded
+ * in between.  RB_EINVAL (nothing stepped): every < 1, nsteps < 0, qpos NULL
+ * with S > 0, or a buffer bound below one sample. */
+int  rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, double restitution,
+                          double friction, double contact_threshold, double *qpos, double *qvel,
+                          int64_t *n_failed);
 
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do

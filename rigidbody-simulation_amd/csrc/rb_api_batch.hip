@@ -3,6 +3,7 @@
 // environment e at slot e * M + b of every device row.  All work is enqueued
 // on the batch's own stream; every entry point returns after it finished.
 #include "rb_host.hpp"
+#include "rb_sampleplan.hpp"
 
 using namespace rb::host;
 
@@ -27,6 +28,16 @@ struct rb_batch {
     int64_t io_rows = 0;
     int64_t *ids = nullptr;                     // device copy of an env_ids list
     int64_t ids_cap = 0;
+    // contact law (rb_batch_set_contact_law)
+    int32_t law = RB_LAW_MUJOCO;
+    double tol = 0.01;
+    double rmax = 0.0;                          // largest bounding radius
+    // sampled runs (rb_batch_run_sampled): one allocation, first the sample
+    // slots the recording kernels fill (the batch's real type), then the
+    // boundary rows of as many samples (double), allocated on first use
+    char *samp = nullptr;
+    size_t samp_bytes = 0;                      // allocated
+    size_t samp_limit = (size_t)256 << 20;      // RBHIP_BATCH_SAMPLE_BYTES
 };
 
 namespace {
@@ -36,7 +47,7 @@ void free_batch(rb_batch *b) {
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids};
+                    b->io_q, b->io_v, b->ids, b->samp};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -53,9 +64,17 @@ double batch_bound_of(int32_t kind, const double *s) {
     return kind == RB_BODY_SPHERE ? s[0] : sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
 }
 
-// the cell size of a world of these bodies (upload_consts): the position
-// check of a step uses the same predicate
-void batch_set_rmax(rb_batch *b, double rmax) { b->inv_cs = 1.0 / (rmax > 0 ? 4.0 * rmax * 1.001 : 1.0); }
+// the cell size of a world of these bodies (upload_consts; under the two-ball
+// law rb_set_contact_law's, from the reach 2 rmax + tol): the position check
+// of a step uses the same predicate
+void batch_set_cell(rb_batch *b) {
+    if (b->law == RB_LAW_BALLS) {
+        const double reach = 2.0 * b->rmax + b->tol;
+        b->inv_cs = 1.0 / (reach > 0 ? 2.0 * reach * 1.001 : 1.0);
+    } else {
+        b->inv_cs = 1.0 / (b->rmax > 0 ? 4.0 * b->rmax * 1.001 : 1.0);
+    }
+}
 
 // row r (of the 8 constant rows) <- src[slot * stride + off], as the batch's real type
 int batch_put_row(rb_batch *b, int row, const double *src, int stride, int off) {
@@ -101,7 +120,42 @@ template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double
     for (int d = 0; d < 3; ++d) p.g[d] = (T)b->g[d];
     p.dt = (T)dt; p.e = (T)e; p.mu = (T)mu; p.thr = (T)thr;
     p.inv_cs = (T)b->inv_cs;
+    p.tol = (T)b->tol;
+    p.ground = b->n_planes == 1;
     return p;
+}
+
+int batch_check_step(const rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr) {
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (nsteps < 0) return fail(RB_EINVAL, "nsteps < 0");
+    if (!(dt > 0) || !(e >= 0) || !(mu >= 0) || !(thr >= 0))
+        return fail(RB_EINVAL, "invalid step parameters dt=%g e=%g mu=%g thr=%g", dt, e, mu, thr);
+    return RB_OK;
+}
+
+// the environments failed so far, as rb_batch_step reports them
+int batch_report(rb_batch *b, int64_t *n_failed) {
+    int32_t cnt = 0;
+    HIPCHK(hipMemsetAsync(b->count, 0, sizeof(int32_t), b->stream));
+    HIPCHK(launch_batch_count(b->code, b->E, b->count, b->stream));
+    HIPCHK(hipMemcpyAsync(&cnt, b->count, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (n_failed) {
+        *n_failed = cnt;
+        return RB_OK;
+    }
+    if (cnt > 0)
+        return fail(RB_EDOM, "device: non-finite or out-of-range body position in %d environment(s) (rb_batch_status)", cnt);
+    return RB_OK;
+}
+
+// bytes one sample of the batch takes in the sample buffer: its slot (rounded
+// up to whole doubles, so that the boundary rows behind the slots are aligned)
+// and its boundary rows
+size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
+size_t sample_bytes(const rb_batch *b, int rows) {
+    const size_t vals = (size_t)b->N * (size_t)rows;
+    return align8(vals * (size_t)b->esz) + vals * sizeof(double);
 }
 
 // the listed environments' rows: staging of n * M rows and the ids on the device
@@ -182,6 +236,8 @@ int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
         for (int j = 0; j < 6; ++j) b->planes[k][j] = d->planes[6 * k + j];
     for (int j = 0; j < 3; ++j) b->g[j] = d->gravity[j];
     b->oriented = d->normal_convention == RB_NORMAL_ORIENTED;
+    if (const char *ev = getenv("RBHIP_BATCH_SAMPLE_BYTES"))
+        if (atoll(ev) > 0) b->samp_limit = (size_t)atoll(ev);
     auto bail = [&](int rc) { free_batch(b); return rc; };
     if (hipSetDevice(b->device) != hipSuccess) return bail(fail(RB_ENODEV, "hipSetDevice(%d) failed", b->device));
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
@@ -252,7 +308,8 @@ int rb_batch_set_bodies(rb_batch *b, const double *mass, const double *inertia, 
             if (bound[(size_t)g] > rmax) rmax = bound[(size_t)g];
         }
         WCHK(batch_put_row(b, 7, bound.data(), 1, 0));
-        batch_set_rmax(b, rmax);
+        b->rmax = rmax;
+        batch_set_cell(b);
         // the snapshots carry the bounding radius
         HIPCHK(by_real(b->dtype, [&](auto t) {
             using T = decltype(t);
@@ -302,12 +359,28 @@ int rb_batch_get_state(rb_batch *b, const int64_t *env_ids, int64_t n, double *q
     return RB_OK;
 }
 
-int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr, int64_t *n_failed) {
+int rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol) {
     ApiScope api_scope_(b ? b->device : -1);
     if (!b) return fail(RB_EINVAL, "null batch");
-    if (nsteps < 0) return fail(RB_EINVAL, "nsteps < 0");
-    if (!(dt > 0) || !(e >= 0) || !(mu >= 0) || !(thr >= 0))
-        return fail(RB_EINVAL, "invalid step parameters dt=%g e=%g mu=%g thr=%g", dt, e, mu, thr);
+    if (law != RB_LAW_MUJOCO && law != RB_LAW_BALLS) return fail(RB_EINVAL, "unknown contact law %d", law);
+    if (!(tol >= 0) || !(tol < 1e6)) return fail(RB_EINVAL, "tol must be finite and >= 0");
+    if (law == RB_LAW_BALLS) {
+        if (b->box) return fail(RB_EUNSUPPORTED, "the two-ball law takes spheres only");
+        const double ground[6] = {0, 0, 1, 0, 0, 0};
+        if (b->n_planes > 1 || (b->n_planes == 1 && memcmp(b->planes[0], ground, sizeof(ground)) != 0))
+            return fail(RB_EUNSUPPORTED, "the two-ball law's only plane is the z = 0 ground (ball_collision.py:88-90)");
+    }
+    // both laws keep a ball's true position in the snapshots and neither
+    // caches anything between launches: a switch converts nothing
+    b->law = law;
+    b->tol = tol;
+    batch_set_cell(b);
+    return RB_OK;
+}
+
+int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr, int64_t *n_failed) {
+    ApiScope api_scope_(b ? b->device : -1);
+    WCHK(batch_check_step(b, nsteps, dt, e, mu, thr));
     HIPCHK(hipSetDevice(b->device));
     // launches of at most RB_BATCH_CHUNK steps: the state between two of them
     // is the state between two steps, so the cut changes nothing
@@ -315,21 +388,74 @@ int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, d
         const int32_t k = (int32_t)std::min<int64_t>(left, BATCH_CHUNK);
         HIPCHK(by_real(b->dtype, [&](auto t) {
             using T = decltype(t);
-            return launch_batch_step<T>(batch_params<T>(b, k, dt, e, mu, thr), b->box, b->stream);
+            return launch_batch_step<T>(batch_params<T>(b, k, dt, e, mu, thr), b->box, b->law == RB_LAW_BALLS, false, b->stream);
         }));
     }
-    int32_t cnt = 0;
-    HIPCHK(hipMemsetAsync(b->count, 0, sizeof(int32_t), b->stream));
-    HIPCHK(launch_batch_count(b->code, b->E, b->count, b->stream));
-    HIPCHK(hipMemcpyAsync(&cnt, b->count, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (n_failed) {
-        *n_failed = cnt;
-        return RB_OK;
+    return batch_report(b, n_failed);
+}
+
+int rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, double e, double mu, double thr,
+                         double *qpos, double *qvel, int64_t *n_failed) {
+    ApiScope api_scope_(b ? b->device : -1);
+    WCHK(batch_check_step(b, nsteps, dt, e, mu, thr));
+    if (every < 1) return fail(RB_EINVAL, "every must be >= 1");
+    const int64_t S = nsteps / every;
+    if (S > 0 && !qpos) return fail(RB_EINVAL, "qpos NULL with %lld samples to record", (long long)S);
+    HIPCHK(hipSetDevice(b->device));
+    // phase and period travel as int32: a period past the chunk never samples
+    // inside a launch that does not end on it, so it is clamped per launch below
+    const int rows = qvel ? 13 : 7;
+    const size_t per = sample_bytes(b, rows);
+    int64_t fit = 1;
+    if (S > 0) {
+        if (per > b->samp_limit)
+            return fail(RB_EINVAL, "one sample of the batch (%zu bytes) does not fit the sample buffer (%zu bytes: "
+                                   "RBHIP_BATCH_SAMPLE_BYTES)", per, b->samp_limit);
+        // no more slots than a launch index can address, than fit the bound, than the run needs
+        fit = std::min<int64_t>({S, (int64_t)(b->samp_limit / per), (int64_t)INT32_MAX / 2});
+        const size_t need = per * (size_t)fit;
+        if (need > b->samp_bytes) {
+            if (b->samp) { HIPCHK(hipFree(b->samp)); b->samp = nullptr; }
+            b->samp_bytes = 0;
+            HIPCHK(hipMalloc((void **)&b->samp, need));
+            b->samp_bytes = need;
+        }
     }
-    if (cnt > 0)
-        return fail(RB_EDOM, "device: non-finite or out-of-range body position in %d environment(s) (rb_batch_status)", cnt);
-    return RB_OK;
+    // the slots first, the boundary rows of `fit` samples behind them
+    const size_t N = (size_t)b->N;
+    char *slots = b->samp;
+    double *out_q = reinterpret_cast<double *>(b->samp + align8((size_t)fit * N * rows * b->esz));
+    double *out_v = out_q + (size_t)fit * N * 7;
+
+    SamplePlan plan(nsteps, every, BATCH_CHUNK, fit);
+    SampleLaunch l;
+    while (plan.next(l)) {
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            BatchParams<T> p = batch_params<T>(b, (int32_t)l.steps, dt, e, mu, thr);
+            if (l.samples == 0)          // nothing to record in this launch: the plain instance
+                return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, false, b->stream);
+            p.samp = reinterpret_cast<T *>(slots);
+            p.every = (int32_t)std::min<int64_t>(every, BATCH_CHUNK + 1);   // (a second sample lies past the launch)
+            p.phase = (int32_t)l.phase;                                     // (<= steps <= RB_BATCH_CHUNK here)
+            p.samp_first = (int32_t)l.first;
+            p.samp_slots = (int32_t)fit;
+            p.samp_rows = rows;
+            return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, true, b->stream);
+        }));
+        if (l.drain == 0) continue;
+        // a plain synchronous drain: transpose, download, wait
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_batch_samples_out<T>(reinterpret_cast<const T *>(slots), 0, (int32_t)l.drain, rows, b->N, out_q,
+                                               out_v, b->stream);
+        }));
+        const size_t n = (size_t)l.drain * N, at = (size_t)l.drain_at * N;
+        HIPCHK(hipMemcpyAsync(qpos + 7 * at, out_q, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, b->stream));
+        if (qvel) HIPCHK(hipMemcpyAsync(qvel + 6 * at, out_v, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return batch_report(b, n_failed);
 }
 
 int rb_batch_status(rb_batch *b, int32_t *code, int64_t *steps_done) {

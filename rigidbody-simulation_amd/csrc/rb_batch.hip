@@ -12,16 +12,40 @@
 // constants of a body once, runs up to RB_BATCH_CHUNK steps in registers and
 // stores once.  Each step is body_update's sequence (rb_kernels.hip) built
 // from the same functions (rb_device.hpp, rb_body.hpp), so an environment
-// steps bit-identically to a world of the same scene.
+// steps bit-identically to a world of the same scene.  The two-ball law
+// (batch_balls_kernel) has the same shape, built from rb_balls.hpp.
+//
+// Sampled runs (rb_batch_run_sampled) launch the recording instances (REC):
+// inside the register loop, after every every-th step of the run, a lane
+// stores its committed state into a slot of the sample buffer, laid out as
+// the state rows are (rows of E * M reals per slot: a wave's stores are
+// contiguous); batch_samples_out_kernel turns slots into the boundary's rows.
 #include "rb_device.hpp"
 #include "rb_grid.hpp"
 #include "rb_internal.hpp"
 #include "rb_body.hpp"
+#include "rb_balls.hpp"
 
 namespace rb {
 
+// a lane's committed state into slot `slot` of the sample buffer
+template <typename T>
+__device__ __forceinline__ void sample_store(const BatchParams<T> &p, int32_t slot, int64_t g, const V3<T> &x,
+                                             const Q4<T> &q, const V3<T> &v, const V3<T> &w) {
+    if (slot < 0 || slot >= p.samp_slots) return;      // (the host's plan keeps a launch inside the buffer)
+    const int64_t N = p.E * p.M;
+    T *o = p.samp + (int64_t)slot * p.samp_rows * N + g;
+    o[0] = x.x; o[N] = x.y; o[2 * N] = x.z;
+    o[3 * N] = q.w; o[4 * N] = q.x; o[5 * N] = q.y; o[6 * N] = q.z;
+    if (p.samp_rows == 13) {
+        o[7 * N] = v.x; o[8 * N] = v.y; o[9 * N] = v.z;
+        o[10 * N] = w.x; o[11 * N] = w.y; o[12 * N] = w.z;
+    }
+}
+
 // BOX: the template environment is one box (M == 1); else spheres only
-template <typename T, bool BOX>
+// REC: the recording instance of a sampled run
+template <typename T, bool BOX, bool REC>
 __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> p) {
     __shared__ Snap<T> s_snap[2][BATCH_BLOCK];
     __shared__ int32_t s_fail[BATCH_BLOCK];      // per environment of the wave; sticky within a launch
@@ -69,6 +93,8 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
     s_fail[lane] = 0;
     s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
     __syncthreads();
+
+    int32_t until = p.phase, slot = p.samp_first;   // REC: steps to the next sample, its slot
 
     for (int s = 0; s < p.k; ++s) {
         const Snap<T> *cur = s_snap[s & 1];
@@ -146,6 +172,14 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
             x = xn; q = qn; v = vn; w = wn;
             ++done;
         }
+        // a failed environment's lanes record its frozen state
+        if constexpr (REC) {
+            if (--until == 0) {
+                if (active) sample_store(p, slot, g, x, q, v, w);
+                ++slot;
+                until = p.every;
+            }
+        }
     }
 
     // ---- store once ------------------------------------------------------------
@@ -159,6 +193,177 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
     if (b == 0) {
         if (done > 0) p.steps_done[env] += done;
         if (done < p.k && p.code[env] == 0) p.code[env] = BATCH_EDOM;
+    }
+}
+
+
+// The two-ball law (rb_balls.hpp; ball_collision.py:73-125) with the lane and
+// environment mapping of batch_step_kernel.  The registers hold a ball's true
+// state (x, v, w) and the post-ground state of the coming step (gx, gv, gw:
+// gravity and the ground contact depend on the ball alone), which is what the
+// partners read from LDS: positions and radius in Snap, velocity and spin in
+// Vel, both ping-pong, so a step has one barrier.  A step evaluates every
+// pair (a < b) within reach from the post-ground state of both balls and
+// accumulates this ball's deltas in ascending partner id (ball_body,
+// rb_balls.hip, without grid or partner list), integrates, and runs the next
+// step's ground phase.  Nothing survives a launch but the true state: the
+// first ground phase is run from it, so dt, e and mu may change between calls.
+// The quaternion is never touched (REC loads it to record it).
+template <typename T, bool REC>
+__global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T> p) {
+    __shared__ Snap<T> s_snap[2][BATCH_BLOCK];
+    __shared__ Vel<T> s_vel[2][BATCH_BLOCK];
+    __shared__ T s_mass[BATCH_BLOCK];
+    __shared__ int32_t s_fail[BATCH_BLOCK];      // per environment of the wave; sticky within a launch
+
+    const int lane = threadIdx.x;
+    const int M = p.M;
+    const int epw = BATCH_BLOCK / M;
+    const int el_raw = lane / M;
+    const int b = lane - el_raw * M;
+    const bool active = el_raw < epw && (int64_t)blockIdx.x * epw + el_raw < p.E;   // (idle lanes: batch_step_kernel)
+    const int el = active ? el_raw : 0;
+    const int64_t env = (int64_t)blockIdx.x * epw + el;
+    const int64_t g = active ? env * M + b : 0;
+    const int ebase = el * M;
+
+    // ---- load once ---------------------------------------------------------
+    const Snap<T> self = p.snap[g];
+    V3<T> x = {self.x, self.y, self.z};
+    const T ri = self.r;
+    V3<T> v = {p.st.vx()[g], p.st.vy()[g], p.st.vz()[g]};
+    V3<T> w = {p.st.wx()[g], p.st.wy()[g], p.st.wz()[g]};
+    Q4<T> q = {T(1), T(0), T(0), T(0)};
+    if constexpr (REC) q = {p.st.qw()[g], p.st.qx()[g], p.st.qy()[g], p.st.qz()[g]};
+    const T mi = p.cs.mass()[g];
+    const M3<T> Ii = ball_iinv(mi, ri);          // ball_collision.py:39-41 (the inertia rows are not read)
+    const int64_t ev = active ? env : 0;
+    bool failed = !active || p.code[ev] != 0;
+    int32_t done = 0;
+
+    // the constants ball_ground reads
+    StepParams<T> sp;
+    sp.g[0] = p.g[0]; sp.g[1] = p.g[1]; sp.g[2] = p.g[2];
+    sp.dt = p.dt;
+    sp.e = p.env_e ? p.env_e[ev] : p.e;
+    sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
+    sp.ground = p.ground;
+    const T tol = p.tol;
+
+    // the first step's ground phase, from the true state
+    V3<T> gx = x, gv = v, gw = w;
+    ball_ground(sp, gx, gv, gw, mi, ri, Ii);
+    s_fail[lane] = 0;
+    s_mass[lane] = mi;
+    s_snap[0][lane] = Snap<T>{gx.x, gx.y, gx.z, ri};
+    s_vel[0][lane] = Vel<T>{gv.x, gv.y, gv.z, gw.x, gw.y, gw.z, T(0), T(0)};
+    __syncthreads();
+
+    int32_t until = p.phase, slot = p.samp_first;   // REC: steps to the next sample, its slot
+
+    for (int s = 0; s < p.k; ++s) {
+        const Snap<T> *cur = s_snap[s & 1];
+        const Vel<T> *curv = s_vel[s & 1];
+        int32_t cx, cy, cz;
+        // the positions a world under this law checks: the post-ground ones
+        bool bad = !cell_of(gx.x, gx.y, gx.z, p.inv_cs, cx, cy, cz);
+
+        // ---- every other ball of the environment, ascending id ---------------
+        // (ball_collision.py:100-118; the expressions of ball_body)
+        const V3<T> xo = gx, vo = gv, wo = gw;
+        V3<T> xa = xo, va = vo, wa = wo;
+        for (int j = 0; j < M; ++j) {
+            if (j == b) continue;
+            const Snap<T> sj = cur[ebase + j];
+            const V3<T> xj = {sj.x, sj.y, sj.z};
+            const bool self_a = b < j;
+            if (!(self_a ? ball_hit(xo, ri, xj, sj.r, tol) : ball_hit(xj, sj.r, xo, ri, tol))) continue;
+            const Vel<T> vj = curv[ebase + j];
+            const T mj = s_mass[ebase + j];
+            const V3<T> pa = self_a ? xo : xj, pb = self_a ? xj : xo;
+            const V3<T> vA = self_a ? vo : V3<T>{vj.vx, vj.vy, vj.vz};
+            const V3<T> wA = self_a ? wo : V3<T>{vj.wx, vj.wy, vj.wz};
+            const T ma = self_a ? mi : mj, ra = self_a ? ri : sj.r, rb = self_a ? sj.r : ri;
+            const M3<T> Ia = self_a ? Ii : ball_iinv(mj, sj.r);
+            const V3<T> diff = {pb.x - pa.x, pb.y - pa.y, pb.z - pa.z};         // :100
+            const T dist = sqroot(np_dot(diff, diff));                          // :101
+            const T dd = dist + T(1e-8);
+            const V3<T> n = {diff.x / dd, diff.y / dd, diff.z / dd};            // :104
+            const V3<T> cp = {(pa.x + pb.x) / T(2), (pa.y + pb.y) / T(2), (pa.z + pb.z) / T(2)};   // :105
+            const V3<T> r1 = {cp.x - pa.x, cp.y - pa.y, cp.z - pa.z};           // :106
+            const V3<T> imp = pair_impulse(ma, Ia, vA, wA, r1, n, sp.e, sp.mu); // :109-110
+            const T corr = (((ra + rb) + tol) - dist) / T(2);                   // :116
+            if (self_a) {
+                const V3<T> dw = np_matvec(Ii, np_cross(r1, imp));
+                va = {va.x + imp.x / mi, va.y + imp.y / mi, va.z + imp.z / mi};     // :111
+                wa = {wa.x + dw.x, wa.y + dw.y, wa.z + dw.z};                       // :112
+                xa = {xa.x - corr * n.x, xa.y - corr * n.y, xa.z - corr * n.z};     // :117
+            } else {
+                const V3<T> r2 = {cp.x - pb.x, cp.y - pb.y, cp.z - pb.z};           // :107
+                const V3<T> dw = np_matvec(Ii, np_cross(r2, imp));
+                va = {va.x - imp.x / mi, va.y - imp.y / mi, va.z - imp.z / mi};     // :113
+                wa = {wa.x - dw.x, wa.y - dw.y, wa.z - dw.z};                       // :114
+                xa = {xa.x + corr * n.x, xa.y + corr * n.y, xa.z + corr * n.z};     // :118
+            }
+        }
+
+        // ---- integrate (:121-122): the true end-of-step state ------------------
+        const V3<T> xn = {xa.x + va.x * sp.dt, xa.y + va.y * sp.dt, xa.z + va.z * sp.dt};
+
+        // ---- the next step's ground phase ------------------------------------
+        V3<T> ngx = xn, ngv = va, ngw = wa;
+        ball_ground(sp, ngx, ngv, ngw, mi, ri, Ii);
+        bad = bad || !cell_of(ngx.x, ngx.y, ngx.z, p.inv_cs, cx, cy, cz);
+
+        // a failing ball fails its environment (batch_step_kernel)
+        if (bad && active) s_fail[el] = 1;
+        s_snap[(s + 1) & 1][lane] = Snap<T>{ngx.x, ngx.y, ngx.z, ri};
+        s_vel[(s + 1) & 1][lane] = Vel<T>{ngv.x, ngv.y, ngv.z, ngw.x, ngw.y, ngw.z, T(0), T(0)};
+        __syncthreads();
+        failed = failed || s_fail[el] != 0;
+        if (!failed) {
+            x = xn; v = va; w = wa;
+            gx = ngx; gv = ngv; gw = ngw;
+            ++done;
+        }
+        if constexpr (REC) {
+            if (--until == 0) {
+                if (active) sample_store(p, slot, g, x, q, v, w);
+                ++slot;
+                until = p.every;
+            }
+        }
+    }
+
+    // ---- store once ------------------------------------------------------------
+    if (!active) return;
+    if (done > 0) {
+        p.snap[g] = Snap<T>{x.x, x.y, x.z, ri};
+        p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
+        p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
+    }
+    if (b == 0) {
+        if (done > 0) p.steps_done[env] += done;
+        if (done < p.k && p.code[env] == 0) p.code[env] = BATCH_EDOM;
+    }
+}
+
+// Slots [first, first + n) of the sample buffer into the boundary's rows (the
+// layout of rb_batch_get_state, a block of [E * M] rows per sample), in double.
+template <typename T>
+__global__ __launch_bounds__(256) void batch_samples_out_kernel(const T *samp, int32_t first, int64_t total, int32_t rows,
+                                                                int64_t N, double *qpos, double *qvel) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int64_t k = t / N, g = t - k * N;
+    const T *in = samp + (first + k) * rows * N + g;
+    double *q = qpos + 7 * t;
+#pragma unroll
+    for (int d = 0; d < 7; ++d) q[d] = (double)in[d * N];
+    if (rows == 13) {
+        double *v = qvel + 6 * t;
+#pragma unroll
+        for (int d = 0; d < 6; ++d) v[d] = (double)in[(7 + d) * N];
     }
 }
 
@@ -217,12 +422,34 @@ template <typename T> __global__ __launch_bounds__(256) void batch_bound_kernel(
 
 static unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, hipStream_t s) {
+template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, bool balls, bool rec, hipStream_t s) {
     if (p.E <= 0 || p.k <= 0) return hipSuccess;
+    if (balls && box) return hipErrorInvalidValue;
+    if (rec && (!p.samp || p.every < 1 || p.phase < 1 || p.phase > p.every || (p.samp_rows != 7 && p.samp_rows != 13)))
+        return hipErrorInvalidValue;
     const int64_t epw = BATCH_BLOCK / p.M;
     const unsigned blocks = (unsigned)((p.E + epw - 1) / epw);
-    if (box) hipLaunchKernelGGL((batch_step_kernel<T, true>), dim3(blocks), dim3(BATCH_BLOCK), 0, s, p);
-    else hipLaunchKernelGGL((batch_step_kernel<T, false>), dim3(blocks), dim3(BATCH_BLOCK), 0, s, p);
+    const dim3 gr(blocks), bl(BATCH_BLOCK);
+    if (balls) {
+        if (rec) hipLaunchKernelGGL((batch_balls_kernel<T, true>), gr, bl, 0, s, p);
+        else hipLaunchKernelGGL((batch_balls_kernel<T, false>), gr, bl, 0, s, p);
+    } else if (rec) {
+        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, true>), gr, bl, 0, s, p);
+        else hipLaunchKernelGGL((batch_step_kernel<T, false, true>), gr, bl, 0, s, p);
+    } else {
+        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, false>), gr, bl, 0, s, p);
+        else hipLaunchKernelGGL((batch_step_kernel<T, false, false>), gr, bl, 0, s, p);
+    }
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_batch_samples_out(const T *samp, int32_t first, int32_t n, int32_t rows, int64_t N, double *qpos,
+                                    double *qvel, hipStream_t s) {
+    if (n <= 0 || N <= 0) return hipSuccess;
+    if (!samp || !qpos || first < 0 || (rows != 7 && rows != 13) || (rows == 13 && !qvel)) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)n * N;
+    hipLaunchKernelGGL((batch_samples_out_kernel<T>), dim3(blocks256(total)), dim3(256), 0, s, samp, first, total, rows, N,
+                       qpos, qvel);
     return hipGetLastError();
 }
 template <typename T>
@@ -251,8 +478,12 @@ template <typename T> hipError_t launch_batch_bound(Snap<T> *snap, const T *boun
     return hipGetLastError();
 }
 
-template hipError_t launch_batch_step<double>(const BatchParams<double> &, bool, hipStream_t);
-template hipError_t launch_batch_step<float>(const BatchParams<float> &, bool, hipStream_t);
+template hipError_t launch_batch_step<double>(const BatchParams<double> &, bool, bool, bool, hipStream_t);
+template hipError_t launch_batch_step<float>(const BatchParams<float> &, bool, bool, bool, hipStream_t);
+template hipError_t launch_batch_samples_out<double>(const double *, int32_t, int32_t, int32_t, int64_t, double *, double *,
+                                                     hipStream_t);
+template hipError_t launch_batch_samples_out<float>(const float *, int32_t, int32_t, int32_t, int64_t, double *, double *,
+                                                    hipStream_t);
 template hipError_t launch_batch_state_in<double>(const StateIO<double> &, const int64_t *, int64_t, int32_t, hipStream_t);
 template hipError_t launch_batch_state_in<float>(const StateIO<float> &, const int64_t *, int64_t, int32_t, hipStream_t);
 template hipError_t launch_batch_state_out<double>(const StateIO<double> &, const int64_t *, int64_t, int32_t, hipStream_t);

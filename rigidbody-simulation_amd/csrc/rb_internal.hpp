@@ -474,8 +474,26 @@ template <typename T> struct BatchParams {
     T g[3];
     T dt, e, mu, thr;
     T inv_cs;                            // 1 / (4 rmax 1.001): the worlds' cell size, for the position check
+    // two-ball law (batch_balls_kernel)
+    T tol;                               // ball_collision.py:102
+    int32_t ground;                      // the z = 0 ground plane is present
+    // sampled runs (the recording instances only): after every every-th step
+    // a lane stores its committed state into slot samp_first, samp_first + 1,
+    // ... of samp; slot s is samp_rows struct-of-arrays rows of E * M reals
+    // (x y z qw qx qy qz [vx vy vz wx wy wz]) from samp + s * samp_rows * E * M
+    T *samp;
+    int32_t every, phase;                // the sampling period; this launch's step `phase` (1-based) is its first sample
+    int32_t samp_first, samp_slots;      // first slot of this launch; slots the buffer has
+    int32_t samp_rows;                   // 7, or 13 with velocities
 };
-template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, hipStream_t s);
+// what rb_batch_step and rb_batch_run_sampled launch: the default law's kernel
+// (spheres or the one box), or the two-ball law's; rec: the recording instance
+template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, bool balls, bool rec, hipStream_t s);
+// slots [first, first + n) of the sample buffer -> the boundary's rows, in
+// double: qpos [n][E * M][7] and (rows == 13) qvel [n][E * M][6]
+template <typename T>
+hipError_t launch_batch_samples_out(const T *samp, int32_t first, int32_t n, int32_t rows, int64_t N, double *qpos,
+                                    double *qvel, hipStream_t s);
 template <typename T>
 hipError_t launch_batch_state_in(const StateIO<T> &p, const int64_t *ids, int64_t n, int32_t M, hipStream_t s);
 template <typename T>

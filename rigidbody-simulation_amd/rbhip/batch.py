@@ -5,8 +5,11 @@ The reference's scenes hold 1 to 4 bodies and are studied one knob per run
 (src/config/sim_overrides.py; the velocity variants under
 data/plots/single_sphere/).  A BatchWorld is n_envs replicas of one such
 scene, each with its own restitution, friction, body constants and state;
-every environment steps bit-identically to a World of the same scene.
-Arrays are environment-major: (E, M, 7) / (E, M, 6).
+every environment steps bit-identically to a World of the same scene, under
+the default contact law or the two-ball law of ball_collision.py.
+Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
+the curves the reference plots (logger_base.py, data_logger.py,
+multi_sphere_logger.py), one per environment, sampled on the device.
 """
 from __future__ import annotations
 
@@ -21,9 +24,14 @@ from .scenes import Scene
 
 class BatchWorld:
     def __init__(self, scene: Scene, n_envs: int, device: int = 0, dtype: str = "f64",
-                 normal_convention: Optional[str] = None):
+                 normal_convention: Optional[str] = None, law: str = "mujoco", tol: float = 0.01):
         """scene: the template environment (1..64 bodies; a box only alone),
-        replicated n_envs times with the scene's initial state."""
+        replicated n_envs times with the scene's initial state.
+
+        law: "mujoco" (the per-body law of collision.py /
+        multi_sphere_bounce.py) or "balls" (the symmetric two-ball law of
+        ball_collision.py: spheres only, no plane or the z = 0 ground; tol is
+        its contact margin, ball_collision.py:102).  See set_contact_law()."""
         L = _lib.load()
         self.scene = scene
         self.dtype = dtype
@@ -51,6 +59,12 @@ class BatchWorld:
         self._h = h
         self._L = L
         E, M = self.n_envs, self.n_bodies
+        if law != "mujoco":
+            try:
+                self.set_contact_law(law, tol)
+            except Exception:
+                self.close()
+                raise
         self.set_state(np.broadcast_to(scene.qpos0, (E, M, 7)), np.broadcast_to(scene.qvel0, (E, M, 6)))
 
     # ---- lifetime ---------------------------------------------------------
@@ -70,6 +84,17 @@ class BatchWorld:
 
     def __exit__(self, *exc):
         self.close()
+
+    # ---- contact law --------------------------------------------------------
+    def set_contact_law(self, law: str, tol: float = 0.01):
+        """"mujoco" or "balls" (as World.set_contact_law).  Under "balls" the
+        threshold given to step() and the inertia rows of set_bodies() are
+        ignored: the law derives the inverse inertia from mass and radius
+        (ball_collision.py:39-41).  The law may be switched between calls."""
+        code = {"mujoco": _lib.RB_LAW_MUJOCO, "balls": _lib.RB_LAW_BALLS}.get(law, law)
+        if not isinstance(code, int):
+            raise ValueError(f"unknown contact law {law!r}")
+        _lib.check(self._L.rb_batch_set_contact_law(self._h, code, float(tol)), "rb_batch_set_contact_law")
 
     # ---- per-environment constants ----------------------------------------
     def _arr(self, a, shape):
@@ -128,6 +153,25 @@ class BatchWorld:
         nf = C.c_int64()
         _lib.check(self._L.rb_batch_step(self._h, int(nsteps), *p, C.byref(nf)), "rb_batch_step")
         return nf.value
+
+    def run_sampled(self, nsteps: int, every: int, velocities: bool = True, dt=None, restitution=None,
+                    friction=None, threshold=None):
+        """Step nsteps times as step() does and record every environment's
+        state after every every-th step, on the device: one launch per 256
+        steps instead of one launch, one sync and one download per sample.
+        Returns (qpos (S, E, M, 7), qvel (S, E, M, 6) or None, n_failed) with
+        S = nsteps // every; sample s is the state after step (s + 1) * every
+        of this call, word for word what step(every) + get_state() returns.  A
+        failed environment's rows repeat its frozen state."""
+        p = self._params(dt, restitution, friction, threshold)
+        nsteps, every = int(nsteps), int(every)
+        S = nsteps // every if every >= 1 and nsteps >= 0 else 0
+        q = np.zeros((S, self.n_envs, self.n_bodies, 7))
+        v = np.zeros((S, self.n_envs, self.n_bodies, 6)) if velocities else None
+        nf = C.c_int64()
+        _lib.check(self._L.rb_batch_run_sampled(self._h, nsteps, every, *p, _lib.ptr(q), _lib.ptr(v), C.byref(nf)),
+                   "rb_batch_run_sampled")
+        return q, v, nf.value
 
     def status(self):
         """(code (E,) int32: 0 or RB_EDOM (-33); steps_done (E,) int64)."""

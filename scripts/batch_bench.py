@@ -11,6 +11,13 @@ spread is visible.  In the same run one World(multi_sphere4) steps `--steps`
 steps the same number of times: without batches that is the only way to run
 the scene, one World call per environment.
 
+--law balls: the same measurement on the reference's ball_collision scene
+(two balls, the two-ball law) against one World(law="balls").
+
+--sampled EVERY: instead, the time of run_sampled(steps, EVERY) against the
+loop it replaces, step(EVERY) + get_state() per sample, on the same batch and
+start state (seconds per run; bytes sampled per second next to it).
+
 Prints one JSON line and writes it to --out (default
 profiles/batch/batch_bench.json).  Needs the GPU: there is no fallback.
 """
@@ -31,10 +38,15 @@ def _summary(rates):
     return dict(median=r[len(r) // 2], min=r[0], max=r[-1], reps=rates)
 
 
-def bench_batch(rb, sc, E, steps, reps, dtype):
+def _batch(rb, sc, E, dtype, law):
+    # (the default law through the constructor every version of the library has)
+    return rb.BatchWorld(sc, E, dtype=dtype) if law == "mujoco" else rb.BatchWorld(sc, E, dtype=dtype, law=law)
+
+
+def bench_batch(rb, sc, E, steps, reps, dtype, law="mujoco"):
     q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
     v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
-    with rb.BatchWorld(sc, E, dtype=dtype) as b:
+    with _batch(rb, sc, E, dtype, law) as b:
         b.set_params(restitution=np.linspace(0.5, 1.0, E))
         b.step(steps)                                   # warm-up
         rates = []
@@ -49,8 +61,60 @@ def bench_batch(rb, sc, E, steps, reps, dtype):
     return _summary(rates)
 
 
-def bench_world(rb, sc, steps, reps, dtype):
-    with rb.World(sc, dtype=dtype) as w:
+def bench_sampled(rb, sc, E, steps, every, reps, dtype, law="mujoco"):
+    """Seconds per run of run_sampled(steps, every) and of the loop it
+    replaces, alternating, from the same start state; the two must return the
+    same words."""
+    q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
+    v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
+    S = steps // every
+
+    def loop(b):
+        sq = np.zeros((S, E, sc.n, 7))
+        sv = np.zeros((S, E, sc.n, 6))
+        for s in range(S):
+            b.step(every)
+            sq[s], sv[s] = b.get_state()
+        b.step(steps - S * every)
+        return sq, sv
+
+    with _batch(rb, sc, E, dtype, law) as b:
+        b.set_params(restitution=np.linspace(0.5, 1.0, E))
+        b.set_state(q, v)
+        lq, lv = loop(b)                                # warm-up of both, and the comparison
+        b.set_state(q, v)
+        sq, sv, _ = b.run_sampled(steps, every)
+        same = bool(np.array_equal(sq.view(np.uint64), lq.view(np.uint64)) and
+                    np.array_equal(sv.view(np.uint64), lv.view(np.uint64)))
+        del lq, lv, sq, sv
+        t_loop, t_samp = [], []
+        for _ in range(reps):
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            loop(b)
+            t_loop.append(time.perf_counter() - t0)
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            b.run_sampled(steps, every)
+            t_samp.append(time.perf_counter() - t0)
+        t_plain = []
+        for _ in range(reps):
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            b.step(steps)
+            t_plain.append(time.perf_counter() - t0)
+    nbytes = S * E * sc.n * 13 * 8                      # what reaches the caller
+    out = dict(samples=S, bytes=nbytes, identical=same, loop_s=_summary(t_loop), sampled_s=_summary(t_samp),
+               step_only_s=_summary(t_plain))
+    out["sampled_bytes_per_s"] = nbytes / out["sampled_s"]["median"] if S else 0.0
+    out["loop_bytes_per_s"] = nbytes / out["loop_s"]["median"] if S else 0.0
+    out["speedup_median"] = out["loop_s"]["median"] / out["sampled_s"]["median"]
+    out["slowest_sampled_beats_fastest_loop"] = out["sampled_s"]["max"] < out["loop_s"]["min"]
+    return out
+
+
+def bench_world(rb, sc, steps, reps, dtype, law="mujoco"):
+    with (rb.World(sc, dtype=dtype) if law == "mujoco" else rb.World(sc, dtype=dtype, law=law)) as w:
         w.step(steps)                                   # warm-up (captures the step graph)
         rates = []
         for _ in range(reps):
@@ -67,21 +131,33 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--law", default="mujoco", choices=["mujoco", "balls"],
+                    help="balls: scene ball_collision under the two-ball law")
+    ap.add_argument("--sampled", type=int, default=0, metavar="EVERY",
+                    help="time run_sampled(steps, EVERY) against step(EVERY) + get_state() in a loop")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "batch_bench.json"))
     a = ap.parse_args()
 
     import rbhip
     from rbhip import scenes
     rbhip.load()
-    sc = scenes.multi_sphere4()
-    res = dict(bench="batch_bench", scene="multi_sphere4", bodies_per_env=sc.n, dtype=a.dtype, steps=a.steps,
-               unit="environment-steps per second", version=rbhip.load().rb_version().decode())
-    res["world"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype)
-    res["batch"] = {str(E): bench_batch(rbhip, sc, E, a.steps, a.reps, a.dtype) for E in a.envs}
-    res["world_after"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype)
-    w = res["world"]["median"]
-    res["ratio_vs_world"] = {E: dict(median=r["median"] / w, min=r["min"] / w, max=r["max"] / w)
-                             for E, r in res["batch"].items()}
+    sc = scenes.ball_collision() if a.law == "balls" else scenes.multi_sphere4()
+    res = dict(bench="batch_bench", scene=sc.name if a.law == "balls" else "multi_sphere4", bodies_per_env=sc.n,
+               dtype=a.dtype, steps=a.steps, unit="environment-steps per second",
+               version=rbhip.load().rb_version().decode())
+    if a.law != "mujoco":
+        res["law"] = a.law
+    if a.sampled:
+        res["unit"] = "seconds per run"
+        res["every"] = a.sampled
+        res["sampled"] = {str(E): bench_sampled(rbhip, sc, E, a.steps, a.sampled, a.reps, a.dtype, a.law) for E in a.envs}
+    else:
+        res["world"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, a.law)
+        res["batch"] = {str(E): bench_batch(rbhip, sc, E, a.steps, a.reps, a.dtype, a.law) for E in a.envs}
+        res["world_after"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, a.law)
+        w = res["world"]["median"]
+        res["ratio_vs_world"] = {E: dict(median=r["median"] / w, min=r["min"] / w, max=r["max"] / w)
+                                 for E, r in res["batch"].items()}
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
