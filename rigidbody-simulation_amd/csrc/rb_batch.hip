@@ -10,8 +10,8 @@
 // body of its own environment (at most 63) against the step-start snapshots,
 // which ping-pong in LDS.  A launch loads the 13 state values and the
 // constants of a body once, runs up to RB_BATCH_CHUNK steps in registers and
-// stores once.  Each step is body_update's sequence (rb_kernels.hip) built
-// from the same functions (rb_device.hpp, rb_body.hpp), so an environment
+// stores once.  Each step is body_update's sequence (rb_step.hpp) built
+// from the same functions (rb_body.hpp, rb_device.hpp), so an environment
 // steps bit-identically to a world of the same scene.  The two-ball law
 // (batch_balls_kernel) has the same shape, built from rb_balls.hpp.
 //
@@ -110,30 +110,10 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
         apply_force<T, false>(sp, 0, m, invI, vn, wn);
         const T kk = impulse_k(m);
 
-        // ---- K2: plane contacts, plane order --------------------------------
-        if constexpr (!BOX) {
-            for (int pl = 0; pl < p.n_planes; ++pl) {
-                const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
-                const V3<T> pp = {p.pp[pl][0], p.pp[pl][1], p.pp[pl][2]};
-                Contact<T> con;
-                if (!plane_sphere(pn, pp, x, sz.x, con)) continue;
-                solve_contact(sp, con, x, con.frame, m, kk, invI, vn, wn);
-            }
-        } else {
-            const M3<T> Mb = mj_body_mat(q);
-            for (int pl = 0; pl < p.n_planes; ++pl) {
-                const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
-                const V3<T> dif = {x.x - p.pp[pl][0], x.y - p.pp[pl][1], x.z - p.pp[pl][2]};
-                const T dist = mj_dot(dif, pn);
-                int cnt = 0;
-                for (int c = 0; c < 8 && cnt < 4; ++c) {
-                    Contact<T> con;
-                    if (!plane_box_corner(pn, x, dist, Mb, sz, c, con)) continue;
-                    ++cnt;
-                    solve_contact(sp, con, x, con.frame, m, kk, invI, vn, wn);
-                }
-            }
-        }
+        // ---- K2: plane contacts, plane order (the planes: the batch's) -------
+        int32_t nrec = 0;                        // (sp.rec_count is null: nothing is recorded)
+        if constexpr (!BOX) solve_planes_sphere(sp, p, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
+        else solve_planes_box(sp, p, 0, x, mj_body_mat(q), sz, m, kk, invI, vn, wn, nrec);
 
         // ---- K2: every other body of the environment, ascending id ----------
         if constexpr (!BOX) {
@@ -142,16 +122,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
                 const Snap<T> sj = cur[ebase + j];
                 const V3<T> cj = {sj.x, sj.y, sj.z};
                 if (!sphere_sphere_hit(x, sz.x, cj, sj.r)) continue;
-                Contact<T> con;
-                V3<T> n;
-                if (b < j) {                        // this body is geom1
-                    sphere_sphere(x, sz.x, cj, sj.r, con);
-                    n = sp.oriented ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
-                } else {
-                    sphere_sphere(cj, sj.r, x, sz.x, con);
-                    n = con.frame;
-                }
-                solve_contact(sp, con, x, n, m, kk, invI, vn, wn);
+                solve_sphere_pair(sp, 0, b, j, x, sz.x, cj, sj.r, m, kk, invI, vn, wn, nrec);
             }
         }
 
@@ -369,7 +340,7 @@ __global__ __launch_bounds__(256) void batch_samples_out_kernel(const T *samp, i
 
 // rb_batch_set_state / rb_batch_get_state for a list of environments: row t
 // of the caller's arrays is body t % M of environment ids[t / M].  (All
-// environments in order: state_in_kernel / state_out_kernel, rb_kernels.hip.)
+// environments in order: state_in_kernel / state_out_kernel, rb_io.hip.)
 template <typename T>
 __global__ __launch_bounds__(256) void batch_state_in_kernel(StateIO<T> p, const int64_t *ids, int64_t rows, int32_t M) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 // rb_grid.hpp — the spatial-hash broadphase shared by the step kernels
-// (rb_kernels.hip) and the two-ball law (rb_balls.hip): cell and bucket
+// (rb_step.hpp) and the two-ball law (rb_balls.hip): cell and bucket
 // maps, slot claims and publication, bucket reads, the 2x2x2 neighbourhood
 // and the ascending per-body partner list.  Not part of the public interface.
 #pragma once
@@ -20,12 +20,12 @@
 #define RB_XCD_REMAP 0
 #endif
 
-// diagnostic builds (rb_kernels.hip lists them): 5 = no candidate snapshot
+// diagnostic builds (rb_step.hpp lists them): 5 = no candidate snapshot
 // loads, 6 = no bucket loads for cells below z = 0
 #ifndef RB_ABLATE
 #define RB_ABLATE 0
 #endif
-// per-wave phase stamps (rb_kernels.hip RB_STAMPS builds)
+// per-wave phase stamps (rb_step.hpp RB_STAMPS builds)
 #ifndef STAMP
 #define STAMP(k) do {} while (0)
 #endif
@@ -514,7 +514,7 @@ __device__ __forceinline__ void list_insert_pos(int32_t *s_id, uint8_t *s_didx, 
     ++np_;
 }
 
-// ---- wide one-lane search (one wave per SIMD, rb_kernels.hip step_kernel_wide)
+// ---- wide one-lane search (one wave per SIMD, rb_step_wide.hip step_kernel_wide)
 // A bucket head of 32 bytes: header and the first WIDE_HEAD_IDS ids.
 constexpr int WIDE_HEAD_IDS = 6;                    // (heads are at least 32 bytes: R <= 4)
 #ifndef RB_WIDE_QBATCH

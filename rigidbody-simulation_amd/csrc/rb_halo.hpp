@@ -1,5 +1,5 @@
 // rb_halo.hpp — system-scope word accesses of the peer-to-peer exchanges and
-// the halo push the step kernels run (rb_kernels.hip; the insert and prime
+// the halo push the step kernels run (rb_step.hpp; the insert and prime
 // kernels are in rb_p2p.hip).  Not part of the public interface.
 #pragma once
 

@@ -1,4 +1,4 @@
-// rb_internal.hpp — shared between the kernels (rb_kernels.hip) and the
+// rb_internal.hpp — shared between the kernel units (rb_step*.hip and the rest) and the
 // C-ABI implementation (rb_api_*.hip, which share rb_host.hpp).  Not part of the public interface.
 #pragma once
 
@@ -413,18 +413,22 @@ template <typename T> hipError_t launch_tile_step(const TileParams<T> &p, int ma
 template <typename T> hipError_t launch_tile_build(const TileIO<T> &p, hipStream_t s);   // bins zeroed by the caller
 template <typename T> hipError_t launch_tile_unbin(const TileIO<T> &p, hipStream_t s);
 
-// launchers (rb_kernels.hip)
+// launchers (rb_step.hip, rb_step_wide.hip, rb_io.hip, rb_kat.hip)
 // step kernel forms: one lane per body, 8 lanes per body (small scenes), one
 // lane per body at one wave per SIMD (mid-size scenes)
 enum : int { FORM_ONE = 0, FORM_COOP = 1, FORM_WIDE = 2, FORM_COOP_HELP = 3, FORM_WIDE_HELP = 4, FORM_TILE = 5 };
 // boxes: the box-capable instantiation (box-box / sphere-box narrowphase)
 template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, int form, bool boxes, hipStream_t s);
-// the wide form's kernel alone (its own translation unit: scheduled for memory clauses)
+// the wide form's kernels alone (rb_step_wide.hip, built with the
+// memory-clause scheduling flags).  Declared extern: that unit holds the
+// only instantiations, every other unit calls them
 template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, hipStream_t s);
-template <typename T> hipError_t launch_insert(const InsertParams<T> &p, hipStream_t s);
+extern template hipError_t launch_step_wide<double>(const StepParams<double> &, int, bool, hipStream_t);
+extern template hipError_t launch_step_wide<float>(const StepParams<float> &, int, bool, hipStream_t);
+template <typename T> hipError_t launch_insert(const InsertParams<T> &p, hipStream_t s);   // rb_io.hip
 // rb_set_state / rb_get_state on the device: the reference's AoS rows (qpos
 // stride 7: x y z qw qx qy qz; qvel stride 6: v, w; multi_sphere_bounce.py:85-88)
-// <-> the SoA state rows and the snapshot (rb_kernels.hip)
+// <-> the SoA state rows and the snapshot (rb_io.hip)
 template <typename T> struct StateIO {
     double *qpos, *qvel;               // [N][7], [N][6] (device; rows [lo, lo + n_local) for the state)
     Snap<T> *snap;                     // the current snapshot (every body)

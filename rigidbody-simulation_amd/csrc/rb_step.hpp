@@ -1,4 +1,7 @@
-// rb_kernels.hip — the hot path on gfx950.
+// rb_step.hpp — the hot path on gfx950: the step-kernel body shared by the
+// two step units (rb_step.hip: cooperative, one-lane, box and split forms;
+// rb_step_wide.hip: the wide forms, built with their own scheduling flags).
+// Device code only; included by those two units and nothing else.
 //
 // One launch per simulation step (rb::step_kernel), 64-thread workgroups
 // (one wave):
@@ -20,20 +23,17 @@
 //   Two tables and two snapshots alternate, so a step reads only data no
 //   thread of the same launch writes: Jacobi across bodies, exactly as
 //   multi_sphere_bounce.py:43-46 (one mj_forward per step).
+#pragma once
+
 #include "rb_device.hpp"
 
-// diagnostic build only: per-wave s_memtime stamps at phase boundaries.
-// One unit keeps them (the fp64 wide unit): the host-side name of the
-// buffer must be unique in the library
+// diagnostic build only: per-wave s_memtime stamps at phase boundaries, into
+// rb_stamp_buf, which the including unit defines first (rb_step_wide.hip:
+// the host-side name of the buffer must be unique in the library)
 #ifndef RB_STAMPS
 #define RB_STAMPS 0
 #endif
-#if RB_STAMPS && !(defined(RB_WIDE_UNIT) && RB_WIDE_UNIT == 1 && defined(RB_INST) && RB_INST == 1)
-#undef RB_STAMPS
-#define RB_STAMPS 0
-#endif
 #if RB_STAMPS
-__device__ unsigned long long rb_stamp_buf[1 << 16][16];
 #define STAMP(k)                                                                                  \
     do {                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                        \
@@ -65,15 +65,6 @@ __device__ unsigned long long rb_stamp_buf[1 << 16][16];
 #endif
 
 namespace rb {
-
-template <typename T>
-__global__ __launch_bounds__(256) void insert_kernel(InsertParams<T> p) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= p.count) return;
-    const int64_t id = p.first + k;
-    if (id >= p.skip_lo && id < p.skip_hi) return;
-    insert_id(p.grid, p.tab, p.err, p.snap[id], (uint32_t)id | (p.kind[id] != 0 ? BOX_FLAG : 0u), *p.tab.gen);
-}
 
 // Candidate test shared by every search form: true if the candidate with
 // snapshot s and tagged id tj is a partner of body i — for two spheres the
@@ -307,23 +298,46 @@ template <typename T> struct Lead {
 #define RB_SOLVE_DEPTH 1
 #endif
 
+// body_update's inputs beside the body itself.
+// The sorted partner list: n ids at id[u * stride] (an LDS column, or the
+// split form's per-slot list in HBM); snapshots (PM, partner mode) at
+// pos[u * stride] (LDS, PM = 1: cooperative form), at pos[d * stride] for
+// the discovery index d = didx[u * stride] < WIDE_HPOS (LDS, PM = 2: wide
+// form) or gathered from the step-start snapshot (PM = 0, and PM = 2 past
+// WIDE_HPOS).  PM is a template flag, so LDS accesses stay ds_read (no flat loads).
+template <typename T> struct Partners {
+    int32_t n;
+    const int32_t *id;
+    int64_t stride;
+    const Snap<T> *pos = nullptr;
+    const uint8_t *didx = nullptr;
+};
+// what a helper wave has done for the body already (help_body): its plane
+// contacts, nrec of them recorded
+struct HelpDone {
+    int32_t nrec = 0;
+    bool planes = false;
+};
+// the next step's table: the generation the body inserts with; tab: the table
+// chosen by the step's epoch control word (body_step), else p.next; keep:
+// append steps, the bucket that lists the body already — a body still in it
+// claims and publishes nothing
+template <typename T> struct NextTable {
+    uint32_t gen;
+    const Table<T> *tab = nullptr;
+    uint32_t keep = NO_BUCKET;
+};
+
 // Everything after the contact search for one body (lane): gravity (unless
 // already applied: forced), the Gauss-Seidel solves in canonical order,
-// integration, next-step insert.
-// The sorted partner list: ids at pid[u * stride] (an LDS column, or the
-// split form's per-slot list in HBM); snapshots (PM, partner mode) at
-// ppos[u * stride] (LDS, PM = 1: cooperative form), at ppos[d * stride] for
-// the discovery index d = pdidx[u * stride] < WIDE_HPOS (LDS, PM = 2: wide
-// form) or gathered from the step-start snapshot (PM = 0, and PM = 2 past
-// WIDE_HPOS).  A template flag, so LDS accesses stay ds_read (no flat loads).
+// integration, next-step insert.  poly, ps: the box kernel's clipping
+// polygon column in LDS and its stride (BOXES).
 template <typename T, int PM, bool BOXES = false, int SDEPTH = 1, bool EP = false>
 __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, int32_t i, V3<T> x, int32_t kind,
                                             V3<T> sz, T bi, const BodyIn<T> &in, bool forced, LazyInvI<T> &invI,
-                                            int32_t np_, const int32_t *pid, int64_t stride, const Snap<T> *ppos,
-                                            int tid, int32_t *cell, uint32_t gen_next, T *poly = nullptr,
-                                            int ps = 0, const uint8_t *pdidx = nullptr, int32_t nrec_in = 0,
-                                            bool planes_done = false, const Table<T> *next_tab = nullptr,
-                                            uint32_t keep = NO_BUCKET) {
+                                            const Partners<T> &pa, const HelpDone &help, const NextTable<T> &nx,
+                                            int tid, int32_t *cell, T *poly, int ps) {
+    const int32_t np_ = pa.n;
     const Q4<T> q = in.q;
     V3<T> v = in.v;
     V3<T> w = in.w;
@@ -334,36 +348,13 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     const T k = impulse_k(m);
 
     STAMP(3);
-    int32_t nrec = nrec_in;
+    int32_t nrec = help.nrec;
     // ---- K2: plane contacts, plane order -------------------------------------
-    // (a sphere's already solved by the helper wave when planes_done)
-    if (kind == 0 && !planes_done) {
-        for (int pl = 0; pl < p.n_planes; ++pl) {
-            const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
-            const V3<T> pp = {p.pp[pl][0], p.pp[pl][1], p.pp[pl][2]};
-            Contact<T> con;
-            if (!plane_sphere(pn, pp, x, sz.x, con)) continue;
-            record(p, l, nrec, -1 - pl, 0, con.dist);
-            solve_contact(p, con, x, con.frame, m, k, invI, v, w);
-        }
-    }
+    // (a sphere's already solved by the helper wave when help.planes)
+    if (kind == 0 && !help.planes) solve_planes_sphere(p, p, l, x, sz.x, m, k, invI, v, w, nrec);
     M3<T> M;                                       // box orientation (mj_kinematics of the free joint)
-    if (kind != 0) M = mj_body_mat(q);
-    if (kind != 0 && !planes_done) {               // (a box's corners likewise)
-        for (int pl = 0; pl < p.n_planes; ++pl) {
-            const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
-            const V3<T> dif = {x.x - p.pp[pl][0], x.y - p.pp[pl][1], x.z - p.pp[pl][2]};
-            const T dist = mj_dot(dif, pn);
-            int cnt = 0;
-            for (int c = 0; c < 8 && cnt < 4; ++c) {
-                Contact<T> con;
-                if (!plane_box_corner(pn, x, dist, M, sz, c, con)) continue;
-                ++cnt;
-                record(p, l, nrec, -1 - pl, 1 + c, con.dist);
-                solve_contact(p, con, x, con.frame, m, k, invI, v, w);
-            }
-        }
-    }
+    if (kind != 0) M = mj_body_mat(q);             // (the box narrowphase below needs it too)
+    if (kind != 0 && !help.planes) solve_planes_box(p, p, l, x, M, sz, m, k, invI, v, w, nrec);
 
     // ---- K2: sphere partners in ascending id order ---------------------------
     // (partner snapshots fetched PB at a time; the solve itself is the
@@ -374,15 +365,15 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     auto fetch = [&](int s0, int32_t (&jj)[PB], Snap<T> (&pe)[PB]) {
 #pragma unroll
         for (int u = 0; u < PB; ++u)
-            if (s0 + u < np_) jj[u] = pid[CHK((s0 + u) * stride, 32 * stride)];
+            if (s0 + u < np_) jj[u] = pa.id[CHK((s0 + u) * pa.stride, 32 * pa.stride)];
 #pragma unroll
         for (int u = 0; u < PB; ++u) {
             if (s0 + u >= np_) continue;
             if constexpr (PM == 1) {
-                pe[u] = ppos[(s0 + u) * stride];
+                pe[u] = pa.pos[(s0 + u) * pa.stride];
             } else if constexpr (PM == 2) {
-                const int d = pdidx[(s0 + u) * stride];
-                pe[u] = d < WIDE_HPOS ? ppos[d * stride] : xld(p.snap_cur + CHK(jj[u], p.n_global));
+                const int d = pa.didx[(s0 + u) * pa.stride];
+                pe[u] = d < WIDE_HPOS ? pa.pos[d * pa.stride] : xld(p.snap_cur + CHK(jj[u], p.n_global));
             } else {
                 pe[u] = xld(p.snap_cur + CHK(jj[u], p.n_global));
             }
@@ -458,17 +449,7 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
                     continue;
                 }
             }
-            Contact<T> con;
-            V3<T> n;
-            if (i < j) {                        // this body is geom1
-                sphere_sphere(x, sz.x, cj, rj, con);
-                n = p.oriented ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
-            } else {
-                sphere_sphere(cj, rj, x, sz.x, con);
-                n = con.frame;
-            }
-            record(p, l, nrec, j, 16, con.dist);
-            solve_contact(p, con, x, n, m, k, invI, v, w);
+            solve_sphere_pair(p, l, i, j, x, sz.x, cj, rj, m, k, invI, v, w, nrec);
         }
     }
     if (p.rec_count) p.rec_count[l] = nrec;
@@ -479,7 +460,7 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
         int32_t cx, cy, cz;
         if (cell_of(x.x, x.y, x.z, p.grid.inv_cs, cx, cy, cz)) { cell[3] = cx; cell[4] = cy; cell[5] = cz; }
     }
-    x = {x.x + v.x * p.dt, x.y + v.y * p.dt, x.z + v.z * p.dt};
+    integrate_position(x, v, p.dt);
     Snap<T> sn;
     sn.x = x.x; sn.y = x.y; sn.z = x.z; sn.r = bi;
     // next step's broadphase: the slot atomic goes first (a later load or
@@ -492,22 +473,16 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     constexpr int L = (PM == 2 || (PM == 0 && !BOXES)) ? LAYOUT_LINEAR : LAYOUT_ANY;
     // heads per line: known in the cooperative and wide forms (rb_api_world.hip)
     constexpr int RL = PM == 1 ? 0 : PM == 2 ? 2 : -1;
-    // next_tab: the table chosen by the step's epoch control word (step_body);
-    // keep: append steps, the bucket that lists the body already — a body
-    // still in it claims and publishes nothing
-    const Table<T> &next = next_tab ? *next_tab : p.next;
-    if (next.line) cl = claim_slot<L, RL>(p.grid, next, p.err, sn, gen_next, keep);
+    const Table<T> &next = nx.tab ? *nx.tab : p.next;
+    if (next.line) cl = claim_slot<L, RL>(p.grid, next, p.err, sn, nx.gen, nx.keep);
     wt_store(p.snap_next + i, sn);
     if (p.bounds) {                              // peer-to-peer exchange: this body's new cell
         int32_t cx, cy, cz;
         if (cell_of(sn.x, sn.y, sn.z, p.grid.inv_cs, cx, cy, cz)) { cell[0] = cx; cell[1] = cy; cell[2] = cz; }
     }
     STAMP(5);
-    const Q4<T> res = mj_mulquat(Q4<T>{T(0), w.x, w.y, w.z}, q);
-    Q4<T> qn = {q.w + (T(0.5) * res.w) * p.dt, q.x + (T(0.5) * res.x) * p.dt,
-                q.y + (T(0.5) * res.y) * p.dt, q.z + (T(0.5) * res.z) * p.dt};
-    const T nq = sqroot(fmadd(qn.z, qn.z, fmadd(qn.y, qn.y, fmadd(qn.x, qn.x, qn.w * qn.w))));
-    qn = {qn.w / nq, qn.x / nq, qn.y / nq, qn.z / nq};
+    Q4<T> qn;
+    integrate_orientation(qn, q, w, p.dt);
     wt_store(p.st.vx() + l, v.x); wt_store(p.st.vy() + l, v.y); wt_store(p.st.vz() + l, v.z);
     wt_store(p.st.wx() + l, w.x); wt_store(p.st.wy() + l, w.y); wt_store(p.st.wz() + l, w.z);
     wt_store(p.st.qw() + l, qn.w); wt_store(p.st.qx() + l, qn.x); wt_store(p.st.qy() + l, qn.y);
@@ -698,10 +673,11 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     }
     constexpr int PM = G > 1 ? 1 : (WIDE && RB_WIDE_LDSPOS) ? 2 : 0;
     constexpr int SD = (WIDE && HELP) ? RB_SOLVE_DEPTH : 1;
-    body_update<T, PM, BOXES, SD, EP>(p, l, i, x, kind, sz, bi, in, forced, invI, np_, s_id + slot, NB,
-                                  PM == 2 ? s_hpos + slot : s_pos + slot, tid, cell, gen_next,
-                                  BOXES ? s_poly + slot : nullptr, NB, PM == 2 ? s_didx + slot : nullptr, help_nrec,
-                                  help_planes, EP ? &next : nullptr, ep_append ? b0 : NO_BUCKET);
+    body_update<T, PM, BOXES, SD, EP>(
+        p, l, i, x, kind, sz, bi, in, forced, invI,
+        Partners<T>{np_, s_id + slot, NB, PM == 2 ? s_hpos + slot : s_pos + slot, PM == 2 ? s_didx + slot : nullptr},
+        HelpDone{help_nrec, help_planes}, NextTable<T>{gen_next, EP ? &next : nullptr, ep_append ? b0 : NO_BUCKET},
+        tid, cell, BOXES ? s_poly + slot : nullptr, NB);
 }
 
 // Halo exchange: fold the wave's new cells, given as per-lane boxes
@@ -768,38 +744,16 @@ __device__ __forceinline__ void help_body(const StepParams<T> &p, const Lead<T> 
         if (!p.xfrc) {
             apply_force(p, l, in.m, invI, in.v, in.w);
             // a body's plane contacts come first in its contact order
-            // (body_update: a sphere's one per plane, a box's corners), so
-            // they are solved here too
+            // (rb_body.hpp), so they are solved here
             const int32_t kind = ld.cs.kind[i];
             const Snap<T> self = ld.snap_cur[i];
             const V3<T> x = {self.x, self.y, self.z};
             const T k = impulse_k(in.m);
             if (kind == 0) {
-                const T rad = ld.cs.sx()[i];
-                for (int pl = 0; pl < p.n_planes; ++pl) {
-                    const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
-                    const V3<T> pp = {p.pp[pl][0], p.pp[pl][1], p.pp[pl][2]};
-                    Contact<T> con;
-                    if (!plane_sphere(pn, pp, x, rad, con)) continue;
-                    record(p, l, nrec, -1 - pl, 0, con.dist);
-                    solve_contact(p, con, x, con.frame, in.m, k, invI, in.v, in.w);
-                }
+                solve_planes_sphere(p, p, l, x, ld.cs.sx()[i], in.m, k, invI, in.v, in.w, nrec);
             } else {
                 const V3<T> sz = {ld.cs.sx()[i], ld.cs.sy()[i], ld.cs.sz()[i]};
-                const M3<T> M = mj_body_mat(in.q);
-                for (int pl = 0; pl < p.n_planes; ++pl) {
-                    const V3<T> pn = {p.pn[pl][0], p.pn[pl][1], p.pn[pl][2]};
-                    const V3<T> dif = {x.x - p.pp[pl][0], x.y - p.pp[pl][1], x.z - p.pp[pl][2]};
-                    const T dist = mj_dot(dif, pn);
-                    int cnt = 0;
-                    for (int c = 0; c < 8 && cnt < 4; ++c) {
-                        Contact<T> con;
-                        if (!plane_box_corner(pn, x, dist, M, sz, c, con)) continue;
-                        ++cnt;
-                        record(p, l, nrec, -1 - pl, 1 + c, con.dist);
-                        solve_contact(p, con, x, con.frame, in.m, k, invI, in.v, in.w);
-                    }
-                }
+                solve_planes_box(p, p, l, x, mj_body_mat(in.q), sz, in.m, k, invI, in.v, in.w, nrec);
             }
             planes = true;
         }
@@ -909,494 +863,5 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
         if (p.epoch) *p.epoch += 1;
     }
 }
-
-// The two forms as separate kernels: the one-lane (large-scene) form may be
-// compiled for more waves per SIMD — its dependent random loads want
-// occupancy more than registers — without touching the cooperative form.
-#ifndef RB_MIN_WAVES_G1
-#define RB_MIN_WAVES_G1 1
-#endif
-// the cooperative form fits 3 waves per SIMD without spilling (measured:
-// +9-12% at 32k-65k bodies, unchanged at 4k; 4 waves spill and lose)
-#ifndef RB_MIN_WAVES_COOP
-#define RB_MIN_WAVES_COOP 3
-#endif
-template <typename T, int MAXP>
-__global__ __launch_bounds__(STEP_BLOCK)
-__attribute__((amdgpu_waves_per_eu(MAXP <= 16 ? RB_MIN_WAVES_COOP : 2)))   // 32 partners: 2 fit
-void step_kernel_coop(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                      const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 8, false, false>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
-}
-// the cooperative form with a helper wave per workgroup (help_body): small
-// scenes, whose body waves leave SIMDs idle
-template <typename T, int MAXP>
-__global__ __launch_bounds__(2 * STEP_BLOCK)
-__attribute__((amdgpu_waves_per_eu(MAXP <= 16 ? RB_MIN_WAVES_COOP : 2)))
-void step_kernel_coop_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                           const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 8, false, false, true>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
-}
-template <typename T, int MAXP>
-__global__ __launch_bounds__(STEP_BLOCK)
-#if RB_MIN_WAVES_G1 > 1
-__attribute__((amdgpu_waves_per_eu(RB_MIN_WAVES_G1)))
-#endif
-void step_kernel_one(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                     const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, false, false>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
-}
-// The box kernel (box worlds, after the step kernel): steps the bodies the
-// step kernel deferred — those with a box-involved partner within bounding
-// range — one lane per body with the box narrowphase (rb_boxes.hpp), from
-// the same step-start data, so the step stays Jacobi across bodies.  One
-// wave per SIMD: the narrowphase's registers fit without scratch, and the
-// sphere step kernels keep their occupancy.
-template <typename T, int MAXP>
-__global__ __launch_bounds__(STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void box_kernel(StepParams<T> p) {
-    __shared__ int32_t s_id[MAXP * STEP_BLOCK];
-    __shared__ T s_poly[48 * STEP_BLOCK];
-    const int tid = threadIdx.x;
-    const uint32_t gen = *p.cur.gen;
-    const int32_t n = *p.defer_cnt;
-    int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
-    // halo-exchanging shard: the peers' bounds, read with every lane active
-    int32_t hb[6];
-    const int64_t halo_e = p.halo.mail ? *p.halo.halo_e : 0;
-    const bool halo = p.halo.mail && n > (int32_t)(blockIdx.x * STEP_BLOCK) && halo_bounds(p, halo_e, hb);
-    for (int64_t qi0 = (int64_t)blockIdx.x * STEP_BLOCK; qi0 < n; qi0 += (int64_t)gridDim.x * STEP_BLOCK) {
-        const int64_t qi = qi0 + tid;
-        int32_t cell[6] = {INT32_MAX, 0, 0, 0, 0, 0};
-        int32_t l = 0;
-        // one lane per body: the lane's LDS column (partner list, polygon) is slot = tid
-        if (qi < n) {
-            l = p.defer_q[qi];
-            body_step<T, MAXP, 1, false, true>(p, Lead<T>::of(p), true, l, tid, 0, tid, s_id, nullptr, nullptr, nullptr,
-                                               nullptr, cell, gen, s_poly);
-        }
-        if (halo) halo_push(p, halo_e, cell[0] != INT32_MAX, p.lo + l, cell, hb);   // (every lane of the wave)
-        if (cell[0] != INT32_MAX)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { lo[d] = min(lo[d], cell[d]); hi[d] = max(hi[d], cell[d]); }
-    }
-    // halo exchange: the deferred bodies' new cells (the step kernel folded
-    // only the bodies it stepped itself)
-    if (p.bounds) fold_box(p.bounds, lo, hi);
-    if (blockIdx.x == 0 && tid == 0) *p.defer_reset = 0;    // the next step's queue
-}
-// one wave per SIMD (up to 64 x 1024 owned bodies): every register is free
-template <typename T, int MAXP, bool HALO, bool EP>
-__global__ __launch_bounds__(STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void step_kernel_wide(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                      const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, false, HALO, EP>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
-}
-
-// the wide form with a helper wave per workgroup (help_body): two waves per
-// SIMD, each within 256 registers
-template <typename T, int MAXP, bool HALO, bool EP>
-__global__ __launch_bounds__(2 * STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void step_kernel_wide_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                           const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, true, HALO, EP>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
-}
-
-// ---- split form (large scenes): search kernel + update kernel -------------
-// The fused kernel's register footprint (the f64 solve) caps it at two
-// waves per SIMD, too few to hide the search's dependent random loads.
-// Split, the search runs at high occupancy and hands each body's sorted
-// partner ids to the update through a per-slot list in HBM ([MAXP][S],
-// coalesced by slot).
-template <typename T, int MAXP, int G>
-__global__ __launch_bounds__(STEP_BLOCK) void search_kernel(StepParams<T> p) {
-    constexpr int NB = STEP_BLOCK / G;
-    __shared__ int32_t s_id[MAXP * NB];
-    __shared__ int32_t t_id[G > 1 ? MAXP * NB : 1];
-    __shared__ Snap<T> s_pos[G > 1 ? MAXP * NB : 1];
-    __shared__ Snap<T> t_pos[G > 1 ? MAXP * NB : 1];
-    const int tid = threadIdx.x;
-    const int slot = tid / G, k = tid % G;
-    const int64_t lb = (int64_t)blockIdx.x * NB + slot;
-    const bool active = lb < p.n_local;
-    if (G == 1 && !active) return;
-    const int32_t l = active ? (int32_t)lb : 0;
-    const int32_t i = p.lo + l;
-    const Snap<T> self = p.snap_cur[CHK(i, p.n_global)];
-    const V3<T> x = {self.x, self.y, self.z};
-    const int32_t kind = p.cs.kind[i];
-    const T rad = p.cs.sx()[i];
-    const uint32_t gen = *p.cur.gen;
-    int32_t np_;
-    bool defer = false;                          // split form: sphere worlds only
-    if constexpr (G == 1) np_ = search_partners<T, MAXP, false>(p, i, kind, x, rad, self.r, s_id, tid, gen, defer);
-    else np_ = search_coop<T, MAXP, G, false, -1>(p, active, i, kind, x, rad, self.r, s_id, s_pos, t_id, t_pos, slot, k, tid,
-                                       gen, defer, [] {});
-    if (!active) return;
-    for (int s = k; s < np_; s += G) p.plist[CHK((int64_t)s * p.S + l, (int64_t)MAXP * p.S)] = s_id[s * NB + slot];
-    if (k == 0) p.plist_cnt[CHK(l, p.S)] = np_;
-}
-
-template <typename T>
-__global__ __launch_bounds__(STEP_BLOCK) void update_kernel(StepParams<T> p) {
-    const int tid = threadIdx.x;
-    const int64_t gt = (int64_t)blockIdx.x * STEP_BLOCK + tid;
-    const int64_t lb = gt;
-    int32_t cell[6] = {INT32_MAX, 0, 0, 0, 0, 0};
-    const uint32_t gen_next = *p.cur.gen + 1u;
-    const int64_t halo_e = p.halo.mail ? *p.halo.halo_e : 0;
-    if (p.next.line && blockIdx.x == 0 && tid == 0) *p.next.gen = gen_next;
-    if (lb < p.n_local) {
-        const int32_t l = (int32_t)lb, i = p.lo + l;
-        const Snap<T> self = p.snap_cur[CHK(i, p.n_global)];
-        const V3<T> x = {self.x, self.y, self.z};
-        const int32_t kind = p.cs.kind[i];
-        const V3<T> sz = {p.cs.sx()[i], kind != 0 ? p.cs.sy()[i] : T(0), kind != 0 ? p.cs.sz()[i] : T(0)};
-        const BodyIn<T> in = load_body(p, l, i);
-        LazyInvI<T> invI;
-        invI.I = in.I;
-        invI.q = in.q;
-        const int32_t np_ = p.plist_cnt[CHK(l, p.S)];
-        if (RB_BOUNDS && np_ > 16) printf("RB_BOUNDS np_ %d at l %d\n", np_, l);
-        body_update<T, 0>(p, l, i, x, kind, sz, self.r, in, false, invI, np_, p.plist + l, p.S, nullptr, tid,
-                          cell, gen_next);
-    }
-    if (p.bounds) fold_bounds(p.bounds, cell);
-    if (p.halo.mail) {                           // halo-exchanging shard: push to the peers
-        int32_t b[6];
-        if (halo_bounds(p, halo_e, b)) halo_push(p, halo_e, cell[0] != INT32_MAX, (int32_t)(p.lo + lb), cell, b);
-    }
-}
-
-#if RB_STAMPS
-extern "C" int rb_diag_stamps(unsigned long long *out, int nblocks) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rb_stamp_buf), sizeof(unsigned long long) * 16 * nblocks);
-}
-#endif
-
-// ---- known-answer kernels ----------------------------------------------
-template <typename T>
-__global__ void kat_impulse_kernel(int64_t n, const double *in, double *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const double *a = in + 24 * c;
-    const T m = (T)a[0], e = (T)a[1], mu = (T)a[2];
-    V3<T> v = {(T)a[3], (T)a[4], (T)a[5]}, w = {(T)a[6], (T)a[7], (T)a[8]};
-    const V3<T> r = {(T)a[9], (T)a[10], (T)a[11]}, nn = {(T)a[12], (T)a[13], (T)a[14]};
-    M3<T> Iw;
-    for (int k = 0; k < 9; ++k) Iw.a[k] = (T)a[15 + k];
-    const M3<T> invI = np_inv3(Iw);
-    T jn;
-    V3<T> jt;
-    impulse(impulse_k(m), v, w, r, nn, e, mu, jn, jt);
-    apply(v, w, m, invI, r, nn, jn, jt);      // the reference always applies
-    double *o = out + 10 * c;
-    o[0] = jn; o[1] = jt.x; o[2] = jt.y; o[3] = jt.z;
-    o[4] = v.x; o[5] = v.y; o[6] = v.z; o[7] = w.x; o[8] = w.y; o[9] = w.z;
-}
-
-template <typename T>
-__global__ void kat_inertia_kernel(int64_t n, const double *in, double *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const double *a = in + 7 * c;
-    const M3<T> Iw = inertia_world(V3<T>{(T)a[0], (T)a[1], (T)a[2]}, Q4<T>{(T)a[3], (T)a[4], (T)a[5], (T)a[6]});
-    const M3<T> Ii = np_inv3(Iw);
-    for (int k = 0; k < 9; ++k) { out[18 * c + k] = Iw.a[k]; out[18 * c + 9 + k] = Ii.a[k]; }
-}
-
-template <typename T>
-__global__ void kat_apply_kernel(int64_t n, const double *in, double *out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const double *a = in + 26 * c;
-    const T m = (T)a[0];
-    V3<T> v = {(T)a[1], (T)a[2], (T)a[3]}, w = {(T)a[4], (T)a[5], (T)a[6]};
-    const V3<T> r = {(T)a[7], (T)a[8], (T)a[9]}, nn = {(T)a[10], (T)a[11], (T)a[12]};
-    const T jn = (T)a[13];
-    const V3<T> jt = {(T)a[14], (T)a[15], (T)a[16]};
-    M3<T> Iw;
-    for (int k = 0; k < 9; ++k) Iw.a[k] = (T)a[17 + k];
-    apply(v, w, m, np_inv3(Iw), r, nn, jn, jt);
-    double *o = out + 6 * c;
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = w.x; o[4] = w.y; o[5] = w.z;
-}
-
-// in[22] = kind1, kind2, c1[3], q1[4], s1[3], c2[3], q2[4], s2[3] (body 1 =
-// lower id) -> out[33] = count, then per contact dist, pos[3], frame[3], kind
-template <typename T>
-__global__ __launch_bounds__(64) void kat_narrow_kernel(int64_t n, const double *in, double *out) {
-    __shared__ T s_poly[48 * 64];
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const double *a = in + 22 * c;
-    double *o = out + 33 * c;
-    for (int k = 0; k < 33; ++k) o[k] = 0;
-    const int k1 = (int)a[0], k2 = (int)a[1];
-    const V3<T> c1 = {(T)a[2], (T)a[3], (T)a[4]}, c2 = {(T)a[12], (T)a[13], (T)a[14]};
-    const Q4<T> q1 = {(T)a[5], (T)a[6], (T)a[7], (T)a[8]}, q2 = {(T)a[15], (T)a[16], (T)a[17], (T)a[18]};
-    const V3<T> s1 = {(T)a[9], (T)a[10], (T)a[11]}, s2 = {(T)a[19], (T)a[20], (T)a[21]};
-    int m = 0;
-    auto emit = [&](const Contact<T> &con, int ck) {
-        double *r = o + 1 + 8 * m;
-        r[0] = (double)con.dist;
-        r[1] = (double)con.pos.x; r[2] = (double)con.pos.y; r[3] = (double)con.pos.z;
-        r[4] = (double)con.frame.x; r[5] = (double)con.frame.y; r[6] = (double)con.frame.z;
-        r[7] = ck;
-        ++m;
-    };
-    Contact<T> con;
-    if (k1 == 0 && k2 == 0) {
-        if (sphere_sphere(c1, s1.x, c2, s2.x, con)) emit(con, 16);
-    } else if (k1 == 0) {
-        if (sphere_box(c1, s1.x, c2, mj_body_mat(q2), s2, con)) emit(con, CK_SPHERE_BOX);
-    } else if (k2 == 0) {
-        if (sphere_box(c2, s2.x, c1, mj_body_mat(q1), s1, con)) emit(con, CK_SPHERE_BOX);
-    } else {
-        box_box(c1, mj_body_mat(q1), s1, c2, mj_body_mat(q2), s2, s_poly + threadIdx.x, 64, emit);
-    }
-    o[0] = m;
-}
-
-// ---- launchers ----------------------------------------------------------
-// The wide form's kernels live in their own unit (RB_WIDE_UNIT=1, built with
-// the memory-clause scheduling flags): the other units must call that unit's
-// instantiation, not compile (and, through the linker's choice among weak
-// copies, possibly run) a copy of their own
-#if defined(RB_WIDE_UNIT) && RB_WIDE_UNIT == 0
-extern template hipError_t launch_step_wide<double>(const StepParams<double> &, int, bool, hipStream_t);
-extern template hipError_t launch_step_wide<float>(const StepParams<float> &, int, bool, hipStream_t);
-#endif
-template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, int form, bool boxes, hipStream_t s) {
-    const bool coop = form == FORM_COOP || form == FORM_COOP_HELP;
-    const int nb = coop ? STEP_BLOCK / 8 : STEP_BLOCK;
-    int64_t blocks = (p.n_local + nb - 1) / nb;
-    if (blocks < 1) blocks = 1;
-    const bool split = !coop && p.plist && !boxes;
-    if (boxes && (!p.quat_cur || !p.defer_q || !p.defer_cnt || !p.defer_reset)) return hipErrorInvalidValue;
-    // the cooperative search reads bucket slot snapshots: never launch it
-    // on a table without them
-    if (needs_slot_snapshots(coop, split) && (!p.cur.pos || (p.next.line && !p.next.pos))) return hipErrorInvalidValue;
-    if (split) {
-        constexpr int GS = SPLIT_SEARCH_LANES;
-        const int64_t sblocks = blocks * GS;
-        if (maxp <= 16) hipLaunchKernelGGL((search_kernel<T, 16, GS>), dim3((unsigned)sblocks), dim3(STEP_BLOCK), 0, s, p);
-        else hipLaunchKernelGGL((search_kernel<T, 32, GS>), dim3((unsigned)sblocks), dim3(STEP_BLOCK), 0, s, p);
-        hipLaunchKernelGGL((update_kernel<T>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, p);
-    } else if (coop && form == FORM_COOP_HELP) {   // (box worlds: the box kernel follows)
-        if (maxp <= 16) hipLaunchKernelGGL((step_kernel_coop_help<T, 16>), dim3((unsigned)blocks), dim3(2 * STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-        else hipLaunchKernelGGL((step_kernel_coop_help<T, 32>), dim3((unsigned)blocks), dim3(2 * STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-    } else if (coop) {
-        if (maxp <= 16) hipLaunchKernelGGL((step_kernel_coop<T, 16>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-        else hipLaunchKernelGGL((step_kernel_coop<T, 32>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-    } else if (form == FORM_WIDE || form == FORM_WIDE_HELP) {
-        const hipError_t we = launch_step_wide<T>(p, maxp, form == FORM_WIDE_HELP, s);
-        if (we != hipSuccess) return we;
-    } else {
-        if (maxp <= 16) hipLaunchKernelGGL((step_kernel_one<T, 16>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-        else hipLaunchKernelGGL((step_kernel_one<T, 32>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-    }
-    if (boxes) {
-        const int64_t bb = (p.n_local + STEP_BLOCK - 1) / STEP_BLOCK;
-        const unsigned nbb = (unsigned)(bb < 1 ? 1 : bb > 256 ? 256 : bb);
-        if (maxp <= 16) hipLaunchKernelGGL((box_kernel<T, 16>), dim3(nbb), dim3(STEP_BLOCK), 0, s, p);
-        else hipLaunchKernelGGL((box_kernel<T, 32>), dim3(nbb), dim3(STEP_BLOCK), 0, s, p);
-    }
-    return hipGetLastError();
-}
-
-// ---- the state across the boundary (rb_set_state / rb_get_state) ----------
-// One lane per body: AoS rows of the caller (qpos[7k], qvel[6k], D1-fixed
-// multi_sphere_bounce.py layout) <-> SoA state rows and snapshot.  The host
-// moves the rows with one DMA each way (pinned staging, rb_api_state.hip).
-template <typename T>
-__global__ __launch_bounds__(256) void state_in_kernel(StateIO<T> p) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= p.N) return;
-    const double *q = p.qpos + 7 * b;
-    p.snap[b] = Snap<T>{(T)q[0], (T)q[1], (T)q[2], p.bound[b]};
-    if (p.quat) {
-        T *o = p.quat + 4 * b;
-        o[0] = (T)q[3]; o[1] = (T)q[4]; o[2] = (T)q[5]; o[3] = (T)q[6];
-    }
-    const int64_t l = b - p.lo;
-    if (l < 0 || l >= p.n_local) return;
-    const double *v = p.qvel + 6 * b;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) p.st.row(d)[l] = (T)q[3 + d];
-#pragma unroll
-    for (int d = 0; d < 6; ++d) p.st.row(4 + d)[l] = (T)v[d];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) p.st.row(10 + d)[l] = (T)q[d];
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void state_out_kernel(StateIO<T> p, int want_q, int want_v) {
-    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= p.n_local) return;
-    const int64_t b = p.lo + l;
-    if (want_q) {
-        double *q = p.qpos + 7 * b;
-        if (p.balls) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) q[d] = (double)p.st.row(10 + d)[l];
-        } else {
-            const Snap<T> s = p.snap[b];
-            q[0] = (double)s.x; q[1] = (double)s.y; q[2] = (double)s.z;
-        }
-#pragma unroll
-        for (int d = 0; d < 4; ++d) q[3 + d] = (double)p.st.row(d)[l];
-    }
-    if (want_v) {
-        double *v = p.qvel + 6 * b;
-#pragma unroll
-        for (int d = 0; d < 6; ++d) v[d] = (double)p.st.row(4 + d)[l];
-    }
-}
-
-// The same rows written straight into mapped pinned host memory (p.qpos /
-// p.qvel host-mapped): one lane per output double, so every wave's store is
-// one contiguous 512 B run across PCIe (a lane per body would scatter 56 B
-// strides); the SoA rows are gathered from HBM instead.
-template <typename T>
-__global__ __launch_bounds__(256) void state_out_flat_kernel(StateIO<T> p, int want_q, int want_v) {
-    const int64_t nq = want_q ? 7 * (int64_t)p.n_local : 0, nv = want_v ? 6 * (int64_t)p.n_local : 0;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nq + nv; e += (int64_t)gridDim.x * blockDim.x) {
-        if (e < nq) {
-            const int64_t l = e / 7;
-            const int d = (int)(e - 7 * l);
-            T x;
-            if (d >= 3) x = p.st.row(d - 3)[l];
-            else if (p.balls) x = p.st.row(10 + d)[l];
-            else x = reinterpret_cast<const T *>(p.snap + p.lo + l)[d];
-            p.qpos[7 * p.lo + e] = (double)x;
-        } else {
-            const int64_t f = e - nq, l = f / 6;
-            const int d = (int)(f - 6 * l);
-            p.qvel[6 * p.lo + f] = (double)p.st.row(4 + d)[l];
-        }
-    }
-}
-
-template <typename T> hipError_t launch_state_in(const StateIO<T> &p, hipStream_t s) {
-    if (p.N <= 0) return hipSuccess;
-    hipLaunchKernelGGL((state_in_kernel<T>), dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-template <typename T> hipError_t launch_state_out(const StateIO<T> &p, bool want_q, bool want_v, hipStream_t s) {
-    if (p.n_local <= 0) return hipSuccess;
-    hipLaunchKernelGGL((state_out_kernel<T>), dim3((unsigned)((p.n_local + 255) / 256)), dim3(256), 0, s, p,
-                       want_q ? 1 : 0, want_v ? 1 : 0);
-    return hipGetLastError();
-}
-template <typename T> hipError_t launch_state_out_flat(const StateIO<T> &p, bool want_q, bool want_v, hipStream_t s) {
-    if (p.n_local <= 0) return hipSuccess;
-    const int64_t n = 13 * (int64_t)p.n_local;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL((state_out_flat_kernel<T>), dim3(blocks), dim3(256), 0, s, p, want_q ? 1 : 0, want_v ? 1 : 0);
-    return hipGetLastError();
-}
-
-template <typename T> hipError_t launch_insert(const InsertParams<T> &p, hipStream_t s) {
-    if (p.count <= 0) return hipSuccess;
-    const int64_t blocks = (p.count + 255) / 256;
-    hipLaunchKernelGGL((insert_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-template <typename T> hipError_t launch_kat_impulse(int64_t n, const double *in, double *out, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL((kat_impulse_kernel<T>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, n, in, out);
-    return hipGetLastError();
-}
-
-template <typename T> hipError_t launch_kat_inertia(int64_t n, const double *in, double *out, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL((kat_inertia_kernel<T>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, n, in, out);
-    return hipGetLastError();
-}
-
-template <typename T> hipError_t launch_kat_apply(int64_t n, const double *in, double *out, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL((kat_apply_kernel<T>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, n, in, out);
-    return hipGetLastError();
-}
-
-template <typename T> hipError_t launch_kat_narrow(int64_t n, const double *in, double *out, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL((kat_narrow_kernel<T>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, n, in, out);
-    return hipGetLastError();
-}
-
-template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, hipStream_t s) {
-    int64_t blocks = (p.n_local + STEP_BLOCK - 1) / STEP_BLOCK;
-    if (blocks < 1) blocks = 1;
-    const bool halo = p.halo.mail != nullptr;
-    // worlds with append epochs (never halo-exchanging: rb_api_step.hip
-    // epoch_eligible) launch the instantiation that carries the epoch code
-    const bool ep = p.ep.ctrl != nullptr && !halo;
-#define RB_WIDE_LAUNCH(K, M, H, E, TH)                                                                            \
-    hipLaunchKernelGGL((K<T, M, H, E>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p)
-#define RB_WIDE_PICK(K, M, TH)                                                                                    \
-    do {                                                                                                          \
-        if (halo) RB_WIDE_LAUNCH(K, M, true, false, TH);                                                          \
-        else if (ep) RB_WIDE_LAUNCH(K, M, false, true, TH);                                                       \
-        else RB_WIDE_LAUNCH(K, M, false, false, TH);                                                              \
-    } while (0)
-    if (help) {
-        if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide_help, 16, 2 * STEP_BLOCK);
-        else RB_WIDE_PICK(step_kernel_wide_help, 32, 2 * STEP_BLOCK);
-        return hipGetLastError();
-    }
-    if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide, 16, STEP_BLOCK);
-    else RB_WIDE_PICK(step_kernel_wide, 32, STEP_BLOCK);
-#undef RB_WIDE_PICK
-#undef RB_WIDE_LAUNCH
-    return hipGetLastError();
-}
-
-// explicit instantiations: RB_INST bit 1 = fp64, bit 2 = fp32 (the Makefile
-// builds the two halves as separate objects, in parallel); RB_WIDE_UNIT: the
-// wide form's kernel only (compiled with its own scheduling flags), else
-// everything else
-#ifndef RB_INST
-#define RB_INST 3
-#endif
-#ifndef RB_WIDE_UNIT
-#define RB_WIDE_UNIT 2                  // both (a one-command build of all sources)
-#endif
-#if RB_WIDE_UNIT >= 1 && (RB_INST & 1)
-template hipError_t launch_step_wide<double>(const StepParams<double> &, int, bool, hipStream_t);
-#endif
-#if RB_WIDE_UNIT >= 1 && (RB_INST & 2)
-template hipError_t launch_step_wide<float>(const StepParams<float> &, int, bool, hipStream_t);
-#endif
-#if RB_WIDE_UNIT != 1 && (RB_INST & 1)
-template hipError_t launch_step<double>(const StepParams<double> &, int, int, bool, hipStream_t);
-template hipError_t launch_kat_narrow<double>(int64_t, const double *, double *, hipStream_t);
-template hipError_t launch_insert<double>(const InsertParams<double> &, hipStream_t);
-template hipError_t launch_state_in<double>(const StateIO<double> &, hipStream_t);
-template hipError_t launch_state_out<double>(const StateIO<double> &, bool, bool, hipStream_t);
-template hipError_t launch_state_out_flat<double>(const StateIO<double> &, bool, bool, hipStream_t);
-template hipError_t launch_kat_impulse<double>(int64_t, const double *, double *, hipStream_t);
-template hipError_t launch_kat_inertia<double>(int64_t, const double *, double *, hipStream_t);
-template hipError_t launch_kat_apply<double>(int64_t, const double *, double *, hipStream_t);
-#endif
-#if RB_WIDE_UNIT != 1 && (RB_INST & 2)
-template hipError_t launch_step<float>(const StepParams<float> &, int, int, bool, hipStream_t);
-template hipError_t launch_kat_narrow<float>(int64_t, const double *, double *, hipStream_t);
-template hipError_t launch_insert<float>(const InsertParams<float> &, hipStream_t);
-template hipError_t launch_state_in<float>(const StateIO<float> &, hipStream_t);
-template hipError_t launch_state_out<float>(const StateIO<float> &, bool, bool, hipStream_t);
-template hipError_t launch_state_out_flat<float>(const StateIO<float> &, bool, bool, hipStream_t);
-template hipError_t launch_kat_impulse<float>(int64_t, const double *, double *, hipStream_t);
-template hipError_t launch_kat_inertia<float>(int64_t, const double *, double *, hipStream_t);
-template hipError_t launch_kat_apply<float>(int64_t, const double *, double *, hipStream_t);
-#endif
 
 }  // namespace rb

@@ -12,7 +12,7 @@
 // with the hashed-cell kernels, so both forms step a body bit-identically;
 // what differs is how a body finds its partners:
 //
-//   hashed cells (rb_kernels.hip): each body reads 8 bucket heads, then
+//   hashed cells (rb_step.hpp): each body reads 8 bucket heads, then
 //     its candidates' snapshots — two dependent rounds of random gathers per
 //     lane — and claims a slot in the next table with two atomics;
 //   tiles (here): a workgroup reads the column tables of its 3 x 3 bins, then
@@ -336,14 +336,7 @@ void tile_step_kernel(const int32_t *cur_off, int32_t ntx, int32_t nty, const ui
         const int32_t id = idw & TILE_ID_MASK;
         apply_force<T, false>(sp, id, m, invI, v, w);   // (no xfrc: tile_eligible)
         kimp = impulse_k(m);
-        for (int pl = 0; pl < sp.n_planes; ++pl) {
-            const V3<T> pn = {sp.pn[pl][0], sp.pn[pl][1], sp.pn[pl][2]};
-            const V3<T> pp = {sp.pp[pl][0], sp.pp[pl][1], sp.pp[pl][2]};
-            Contact<T> con;
-            if (!plane_sphere(pn, pp, x, self.r, con)) continue;
-            record(sp, id, nrec, -1 - pl, 0, con.dist);
-            solve_contact(sp, con, x, con.frame, m, kimp, invI, v, w);
-        }
+        solve_planes_sphere(sp, sp, id, x, self.r, m, kimp, invI, v, w, nrec);   // (records by body id)
     };
     if (own_bin) phys_a();
     TSTAMP(3);
@@ -492,18 +485,7 @@ void tile_step_kernel(const int32_t *cur_off, int32_t ntx, int32_t nty, const ui
             }
             prev = j;
             const Snap<T> c = wpos(f);
-            const V3<T> cj = {c.x, c.y, c.z};
-            Contact<T> con;
-            V3<T> n;
-            if (id < j) {                                // this body is geom1
-                sphere_sphere(x, self.r, cj, c.r, con);
-                n = sp.oriented ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
-            } else {
-                sphere_sphere(cj, c.r, x, self.r, con);
-                n = con.frame;
-            }
-            record(sp, id, nrec, j, 16, con.dist);
-            solve_contact(sp, con, x, n, m, kimp, invI, v, w);
+            solve_sphere_pair(sp, id, id, j, x, self.r, V3<T>{c.x, c.y, c.z}, c.r, m, kimp, invI, v, w, nrec);
         }
         if (sp.rec_count) sp.rec_count[id] = nrec;
         TSTAMP(6);
@@ -660,7 +642,7 @@ __global__ __launch_bounds__(256) void tile_unbin_kernel(TileIO<T> p) {
 // ---- launchers ----------------------------------------------------------------
 // the fields the step's first loads need, as leading scalar arguments that
 // gfx950 preloads into SGPRs (the unit is built with
-// -amdgpu-kernarg-preload-count, as the step kernels' Lead in rb_kernels.hip)
+// -amdgpu-kernarg-preload-count, as the step kernels' Lead in rb_step.hpp)
 #define TILE_LEAD(p) (p).cur.off, (p).ntx, (p).nty, (p).gen_cur, (p).sp.err, (p).cur.far_hdr
 template <typename T, int MAXP, int OCC>
 hipError_t launch_tile_step_tc(const TileParams<T> &p, hipStream_t s) {

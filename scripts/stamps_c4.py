@@ -4,7 +4,7 @@ OUT=../../build/stamps.so OBJDIR=build/stamps EXTRA=-DRB_STAMPS=1`).
 C4 (65,536 spheres on the incline) is stepped from t = 0 to `--warm` steps
 (max_partners 32, the bench's c4 world), then one recorded launch; prints
 the phase spans of the slowest blocks and the median, and how many blocks
-are slow.  Phases (rb_kernels.hip STAMP): 0 start, 1 own loads issued,
+are slow.  Phases (rb_step.hpp STAMP): 0 start, 1 own loads issued,
 8 heads back, 9 head candidates tested, 10 rare path done, 2 search done,
 3 forces, 4 solves done, 5 claim + snapshot store, 6 end."""
 import argparse
