@@ -324,7 +324,13 @@ int rb_query(rb_world *w, int64_t *n_owned, int64_t *bytes_per_body_step);
 #define RB_STAT_APPEND_STEPS   19   /* steps that appended to the table they read */
 #define RB_STAT_REBUILD_STEPS  20   /* steps of a world with epochs that rebuilt the next table */
 #define RB_STAT_TABLE_EPOCH    21   /* RBHIP_TABLE_EPOCH: the longest epoch (1: every step rebuilds) */
-#define RB_STATS_COUNT         22
+#define RB_STAT_GRID_LAYOUT    22   /* the cell -> bucket layout word: group shape bits of x, y, z in nibbles
+                                       0-2; bit 24: linear layout, periodic in 2^lx x 2^ly x 2^lz groups
+                                       (nibbles 3-5); bits 25-26: log2 bucket heads per line */
+#define RB_STAT_HELP_SEARCH    23   /* 1: the world's hashed form is wide + helper and shares the contact
+                                       search between its two waves (RBHIP_HELP_SEARCH; 0 in worlds with a
+                                       box body and in every other form) */
+#define RB_STATS_COUNT         24
 int rb_world_stats(rb_world *w, int64_t *out, int32_t n);
 int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches);
 

@@ -168,7 +168,7 @@ int launch_one(rb_world *w, hipStream_t s, int64_t c, double dt, double e, doubl
     const hipError_t r = by_real(w->dtype, [&](auto t) {
         using T = decltype(t);
         const StepParams<T> p = make_step<T>(w, c, dt, e, mu, thr, true);
-        return w->law == RB_LAW_BALLS ? launch_ball_step<T>(p, w->maxp, s) : launch_step<T>(p, w->maxp, form, boxes, s);
+        return w->law == RB_LAW_BALLS ? launch_ball_step<T>(p, w->maxp, s) : launch_step<T>(p, w->maxp, form, boxes, w->help_search, s);
     });
     HIPCHK(r);
     return RB_OK;

@@ -157,10 +157,15 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     // 4,096 8.6 / 10.7 / 11.7 us, 5,184 10.4 / 12.4 / 10.2, 9,216 12.9 /
     // 15.7 / 10.2, 16,384 14.7 (plain) / 12.2; scripts/form_ab.py)
     if (any_box) w->coop_max = 4608;
+    // worlds with boxes keep the helper wave without a share of the search
+    // (C5, 16,384 cubes: about 20 % slower per step with it;
+    // profiles/help_search/shapes_ab.log)
+    if (any_box) w->help_search = false;
     if (const char *ev = getenv("RBHIP_COOP_MAX_BODIES")) w->coop_max = atoll(ev);
     if (const char *ev = getenv("RBHIP_WIDE_MAX_BODIES")) w->wide_max = atoll(ev);
     if (const char *ev = getenv("RBHIP_HELP_MAX_BODIES")) w->help_max = atoll(ev);
     if (const char *ev = getenv("RBHIP_WIDE_HELP")) w->wide_help = atoi(ev) != 0;
+    if (const char *ev = getenv("RBHIP_HELP_SEARCH")) w->help_search = atoi(ev) != 0;
     // the cell-ordered tile form (rb_tiles.hip): RBHIP_TILE = 0 off, 1 every
     // eligible world, -1 auto, the default (eligible worlds of >=
     // RBHIP_TILE_MIN_BODIES bodies, until their first roll-back): it measures
@@ -229,7 +234,17 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
         while ((int64_t(1) << (lg + 1)) <= w->H) ++lg;
         lg -= gbits(gshape);
         const int lz = lg / 3 < 3 ? lg / 3 : 3, lx = (lg - lz + 1) / 2, ly = lg - lz - lx;
-        w->group |= (lx << 12) | (ly << 16) | (lz << 20) | (1 << 24);
+        int l[3] = {lx, ly, lz};
+        // diagnostic: RBHIP_HASH_PERIOD=lx:ly:lz sets the creation-time split
+        // (at most the table's group bits; with RBHIP_FIT_PERIOD=0 it stays).
+        // A zero on an axis whose groups are one cell thick makes a body's
+        // two cells along that axis one bucket (tests of the visit-once rule)
+        if (const char *ev = getenv("RBHIP_HASH_PERIOD")) {
+            int a = 0, b = 0, c = 0;
+            if (sscanf(ev, "%d:%d:%d", &a, &b, &c) == 3 && a >= 0 && b >= 0 && c >= 0 && a <= 15 && b <= 15 && c <= 15 &&
+                a + b + c <= lg) { l[0] = a; l[1] = b; l[2] = c; }
+        }
+        w->group |= (l[0] << 12) | (l[1] << 16) | (l[2] << 20) | (1 << 24);
     }
     // heads per 128-byte line (rb_internal.hpp Table): 4 in wide-form worlds
     // (C3 17.4 -> 16.4 us), 2 in one-lane worlds (1M 0.237 -> 0.225 ms; 4
@@ -482,7 +497,9 @@ int rb_world_stats(rb_world *w, int64_t *out, int32_t n) {
                                        w->tile_stats[0], w->tile_stats[1], w->tile_stats[2], w->tile_stats[3],
                                        (int64_t)w->tile_why_seen, (int64_t)w->tile_ntx * w->tile_nty,
                                        (int64_t)w->tile_tc, tile && w->tile_skip == 0 ? 1 : 0, step_form(w),
-                                       (int64_t)ep_count[0], (int64_t)ep_count[1], (int64_t)w->epoch_max};
+                                       (int64_t)ep_count[0], (int64_t)ep_count[1], (int64_t)w->epoch_max,
+                                       (int64_t)(uint32_t)w->group,
+                                       step_form(w) == FORM_WIDE_HELP && w->help_search ? 1 : 0};
     for (int32_t k = 0; k < n && k < RB_STATS_COUNT; ++k) out[k] = v[k];
     return n < RB_STATS_COUNT ? n : RB_STATS_COUNT;
 }

@@ -546,16 +546,8 @@ template <int S> __device__ __forceinline__ uint32_t head6_id(const Head6 &h) {
 // written back; with s_didx, each sorted entry's discovery index among the
 // first WIDE_HPOS discovered (255 past them), from those ids kept aside.
 constexpr int WIDE_RANK_MAX = 8;                     // longer lists: the bitonic network
-template <int MAXP>
-__device__ __forceinline__ void sort_partners_bitonic(int32_t *s_id, uint8_t *s_didx, int stride, int slot, int32_t np,
-                                                      int32_t nh) {
+template <int MAXP> __device__ __forceinline__ void bitonic_network(int32_t (&a)[MAXP]) {
     static_assert(MAXP == 16 || MAXP == 32, "bitonic: a power of two");
-    int32_t a[MAXP];
-#pragma unroll
-    for (int q = 0; q < MAXP; ++q) a[q] = q < np ? s_id[q * stride + slot] : INT32_MAX;
-    int32_t first[WIDE_HPOS];
-#pragma unroll
-    for (int q = 0; q < WIDE_HPOS; ++q) first[q] = q < nh ? a[q] : -1;
 #pragma unroll
     for (int k = 2; k <= MAXP; k <<= 1)
 #pragma unroll
@@ -570,6 +562,17 @@ __device__ __forceinline__ void sort_partners_bitonic(int32_t *s_id, uint8_t *s_
                     a[l] = up ? hi : lo;
                 }
             }
+}
+template <int MAXP>
+__device__ __forceinline__ void sort_partners_bitonic(int32_t *s_id, uint8_t *s_didx, int stride, int slot, int32_t np,
+                                                      int32_t nh) {
+    int32_t a[MAXP];
+#pragma unroll
+    for (int q = 0; q < MAXP; ++q) a[q] = q < np ? s_id[q * stride + slot] : INT32_MAX;
+    int32_t first[WIDE_HPOS];
+#pragma unroll
+    for (int q = 0; q < WIDE_HPOS; ++q) first[q] = q < nh ? a[q] : -1;
+    bitonic_network<MAXP>(a);
 #pragma unroll
     for (int q = 0; q < MAXP; ++q)
         if (q < np) {
@@ -897,6 +900,263 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
         np_ = w;
     }
     STAMP(10);
+    if (overflow) atomicOr(p.err, ERR_PARTNER_OVERFLOW);
+    return np_;
+}
+
+// ---- shared wide search (step_kernel_wide_help with SHARE, rb_step.hpp)
+// The body's 2x2x2 buckets are searched by two lanes: lane t of the body wave
+// (role 0) takes the four buckets on the body's own side of the split axis —
+// b[0], its step-start bucket, among them — and lane t of the helper wave
+// (role 1) the four on the neighbour side.  The split keeps x-adjacent heads,
+// which share a 128-byte line, in one wave.  Both waves run this one routine
+// (role is wave-uniform, so the selects are scalar).  Each half lists its
+// head ids in its half of the lane's s_cand column (SHARE_HALF rows), tests
+// them and appends its hits unsorted: the body wave fills s_id from row 0 up,
+// the helper from row MAXP - 1 down, and each keeps its first SHARE_HPOS hit
+// snapshots in its half of s_hpos.  Returns the half's hit count (it goes on
+// counting past the rows it may write).  merge_halves then orders the two.
+#ifndef RB_SHARE_AXIS
+#define RB_SHARE_AXIS 1                              // 0: x, 1: y, 2: z
+#endif
+#ifndef RB_SHARE_QBATCH
+#define RB_SHARE_QBATCH 8                            // candidates per round trip (6: C3 12.65 us, 8: 12.51, 12: 12.71)
+#endif
+constexpr int SHARE_BIT = 1 << RB_SHARE_AXIS;
+constexpr int SHARE_QBATCH = RB_SHARE_QBATCH;
+constexpr int SHARE_HALF = WIDE_MAXC / 2;            // head candidates a half lists
+constexpr int SHARE_HPOS = WIDE_HPOS / 2;            // hit snapshots a half keeps
+static_assert(RB_SHARE_AXIS == 1 || RB_SHARE_AXIS == 2, "a split along x parts the heads of one line");
+// own bucket q of a half -> its index among the eight, role 0 (a zero bit put in at the split axis)
+constexpr int share_k0(int q) { return ((q & ~(SHARE_BIT - 1)) << 1) | (q & (SHARE_BIT - 1)); }
+
+template <typename T, int MAXP, bool EP, typename Hit, typename Overlap>
+__device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int32_t i, V3<T> x, int role, int32_t *s_id,
+                                                    uint32_t *s_cand, Snap<T> *s_hpos, int tid, uint32_t gen,
+                                                    const Table<T> &cur, uint32_t &b0, Hit hit, Overlap overlap) {
+    constexpr int NB = STEP_BLOCK;
+    constexpr int QB = SHARE_QBATCH;
+    int32_t cx = 0, cy = 0, cz = 0, sx = 1, sy = 1, sz = 1;
+    // (no early return: overlap() is inlined once; an out-of-domain body
+    // reads valid buckets and counts them as empty)
+    const bool ok = neighbourhood(p, x, cx, cy, cz, sx, sy, sz);
+    if (!ok && role == 0) atomicOr(p.err, ERR_DOMAIN);
+    uint32_t b[8], bo[4];
+    int32_t c[4];
+    Head6 hd[4];
+    neighbour_buckets<LAYOUT_LINEAR>(p.grid, cx, cy, cz, sx, sy, sz, b);
+    constexpr int rl = 2;                         // heads per line: wide-form worlds 4 (rb_api_world.hip)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        bo[q] = role ? b[share_k0(q) | SHARE_BIT] : b[share_k0(q)];
+        hd[q] = bucket_head6(cur, (uint32_t)CHK(bo[q], p.grid.H), rl);
+    }
+    // (an out-of-domain body: cell (0, 0, 0)'s bucket, not NO_BUCKET — it
+    // could only make the body skip its claim, and ERR_DOMAIN discards the step)
+    b0 = b[0];
+    __builtin_amdgcn_sched_barrier(0);            // the head loads issue before the helper's work
+    overlap();
+    STAMP(8);
+    uint32_t *const cand = s_cand + role * (SHARE_HALF * NB) + tid;
+    int32_t n = 0;
+    bool more = false;
+    uint32_t spm = 0;
+    [[maybe_unused]] const uint32_t ng = (uint32_t)p.n_global;   // (search_buckets_wide: appended tables)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        int32_t m = ok ? head_count(hd[q].a, gen) : 0;
+        // visit once: an equal bucket of a lower index among the eight,
+        // whichever wave owns it
+#pragma unroll
+        for (int j = 0; j < (share_k0(q) | SHARE_BIT); ++j)
+            if ((j < share_k0(q) || role) && b[j] == bo[q]) m = 0;
+        c[q] = m;
+        more |= m > WIDE_HEAD_IDS;
+        if (m > 0 && head_spilled(hd[q].a, gen)) spm |= 1u << q;
+#define RB_WIDE_LIST(S)                                                           \
+        {                                                                         \
+            const uint32_t t = head6_id<S>(hd[q]);                                \
+            cand[n * NB] = t;                                                     \
+            n += (S < m && (t & ~BOX_FLAG) != (uint32_t)i && (!EP || (t & ~BOX_FLAG) < ng)) ? 1 : 0; \
+        }
+        RB_WIDE_LIST(0) RB_WIDE_LIST(1) RB_WIDE_LIST(2) RB_WIDE_LIST(3) RB_WIDE_LIST(4) RB_WIDE_LIST(5)
+#undef RB_WIDE_LIST
+    }
+    int32_t np_ = 0;
+    int32_t *const ids = s_id + (role ? (MAXP - 1) * NB : 0) + tid;
+    const int idir = role ? -NB : NB;
+    Snap<T> *const kept = s_hpos + role * (SHARE_HPOS * NB) + tid;
+    auto append = [&](int32_t j, const Snap<T> &sn) {
+        if (np_ < MAXP) ids[np_ * idir] = j;
+        if (RB_WIDE_LDSPOS && np_ < SHARE_HPOS) kept[np_ * NB] = sn;
+        ++np_;
+    };
+    auto batch = [&](int base) {
+        uint32_t tj[QB];
+        Snap<T> sn[QB];
+#pragma unroll
+        for (int u = 0; u < QB; ++u) tj[u] = base + u < n ? cand[(base + u) * NB] : (uint32_t)i;
+#pragma unroll
+        for (int u = 0; u < QB; ++u) {
+            sn[u] = Snap<T>{x.x, x.y, x.z, T(0)};
+            if ((tj[u] & ~BOX_FLAG) != (uint32_t)i) sn[u] = xld(p.snap_cur + CHK(tj[u] & ~BOX_FLAG, p.n_global));
+        }
+#pragma unroll
+        for (int u = 0; u < QB; ++u)
+            if (base + u < n && hit(tj[u], sn[u])) append((int32_t)(tj[u] & ~BOX_FLAG), sn[u]);
+    };
+    batch(0);
+    for (int base = QB; base < n; base += QB) batch(base);
+    STAMP(9);
+    if (RB_WIDE_MORE && more) {
+        // buckets of 7+ bodies: as search_buckets_wide's pipelined rare path, over four buckets
+        int32_t E[4];
+        int32_t e = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            e += c[q] > WIDE_HEAD_IDS ? c[q] - WIDE_HEAD_IDS : 0;
+            E[q] = e;
+        }
+        uint32_t tjn[QB];
+        auto load_ids = [&](int32_t t0) {
+#pragma unroll
+            for (int u = 0; u < QB; ++u) {
+                const int32_t t = t0 + u;
+                uint32_t bk = bo[3];
+                int32_t base = E[2];
+#pragma unroll
+                for (int q = 2; q >= 0; --q)
+                    if (t < E[q]) { bk = bo[q]; base = q ? E[q - 1] : 0; }
+                tjn[u] = t < e ? xld(slot_word(cur, bk, t - base + WIDE_HEAD_IDS, rl)) : (uint32_t)i;
+            }
+        };
+        load_ids(0);
+#pragma unroll 1
+        for (int32_t t0 = 0; t0 < e; t0 += QB) {
+            uint32_t tj[QB];
+#pragma unroll
+            for (int u = 0; u < QB; ++u) tj[u] = (!EP || (tjn[u] & ~BOX_FLAG) < ng) ? tjn[u] : (uint32_t)i;
+            Snap<T> sn[QB];
+#pragma unroll
+            for (int u = 0; u < QB; ++u) {
+                sn[u] = Snap<T>{x.x, x.y, x.z, T(0)};
+                if ((tj[u] & ~BOX_FLAG) != (uint32_t)i) sn[u] = xld(p.snap_cur + CHK(tj[u] & ~BOX_FLAG, p.n_global));
+            }
+            if (t0 + QB < e) load_ids(t0 + QB);
+#pragma unroll
+            for (int u = 0; u < QB; ++u)
+                if (t0 + u < e && hit(tj[u], sn[u])) append((int32_t)(tj[u] & ~BOX_FLAG), sn[u]);
+        }
+    }
+    if (RB_WIDE_MORE && spm) {                        // rarer: ids past full buckets (indices stashed in the half's rows)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cand[q * NB] = bo[q];
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q) {
+            if (!((spm >> q) & 1u)) continue;
+            spill_scan(cur, gen, cand[q * NB], [&](uint32_t t) {
+                const uint32_t j = t & ~BOX_FLAG;
+                if (j == (uint32_t)i || (EP && j >= ng)) return;
+                const Snap<T> sn = xld(p.snap_cur + CHK(j, p.n_global));
+                if (!hit(t, sn)) return;
+                append((int32_t)j, sn);
+            });
+        }
+    }
+    STAMP(10);
+    return np_;
+}
+
+// The body wave, once both halves are done (after the barriers): the two
+// hit lists (na from row 0 up, nb from row MAXP - 1 down) become one list in
+// rows 0.. of s_id, ascending by id, with s_didx mapping each to its kept
+// snapshot's slot (255: not kept) — the orders and the duplicate rule of
+// search_buckets_wide.  The rank sort's scratch is the lane's s_cand column.
+template <typename T, int MAXP, bool EP>
+__device__ __forceinline__ int32_t merge_halves(const StepParams<T> &p, int32_t *s_id, uint32_t *s_cand, uint8_t *s_didx,
+                                                int tid, int32_t na_all, int32_t nb_all, bool appended) {
+    constexpr int NB = STEP_BLOCK;
+    const bool overflow = na_all + nb_all > MAXP;      // (the lists then overlap; the step is discarded)
+    const int32_t na = na_all < MAXP ? na_all : MAXP;
+    const int32_t nb = nb_all < MAXP - na ? nb_all : MAXP - na;
+    int32_t np_ = na + nb;
+    auto row = [&](int u) { return (u < na ? u : MAXP - 1 - (u - na)) * NB + tid; };
+    auto slot_of = [&](int u) {
+        const int h = u < na ? u : u - na;
+        return (uint8_t)(h >= SHARE_HPOS ? 255 : u < na ? h : SHARE_HPOS + h);
+    };
+    if (np_ > WIDE_RANK_MAX) {
+        int32_t a[MAXP];
+#pragma unroll
+        for (int q = 0; q < MAXP; ++q) a[q] = q < np_ ? s_id[row(q)] : INT32_MAX;
+        int32_t first[WIDE_HPOS];
+#pragma unroll
+        for (int f = 0; f < SHARE_HPOS; ++f) {
+            first[f] = f < na ? s_id[f * NB + tid] : -1;
+            first[SHARE_HPOS + f] = f < nb ? s_id[(MAXP - 1 - f) * NB + tid] : -1;
+        }
+        bitonic_network<MAXP>(a);
+#pragma unroll
+        for (int q = 0; q < MAXP; ++q)
+            if (q < np_) {
+                s_id[q * NB + tid] = a[q];
+                if (RB_WIDE_LDSPOS) {
+                    int d = 255;
+#pragma unroll
+                    for (int f = 0; f < WIDE_HPOS; ++f) d = first[f] == a[q] ? f : d;
+                    s_didx[q * NB + tid] = (uint8_t)d;
+                }
+            }
+    } else if (np_ == 2) {
+        const int32_t j0 = s_id[row(0)], j1 = s_id[row(1)];
+        const bool sw = j1 < j0;
+        s_id[tid] = sw ? j1 : j0;
+        s_id[NB + tid] = sw ? j0 : j1;
+        if (RB_WIDE_LDSPOS) {
+            s_didx[tid] = sw ? slot_of(1) : slot_of(0);
+            s_didx[NB + tid] = sw ? slot_of(0) : slot_of(1);
+        }
+    } else if (EP && appended && np_ > 1) {
+        // by rank; equal ids (an appended table's) rank by position (a loop
+        // of its own, as in search_buckets_wide)
+        for (int u = 0; u < np_; ++u) {
+            const int32_t v = s_id[row(u)];
+            int r = 0;
+            for (int q = 0; q < np_; ++q) {
+                const int32_t o = s_id[row(q)];
+                r += (o < v || (o == v && q < u)) ? 1 : 0;
+            }
+            s_cand[r * NB + tid] = (uint32_t)v;
+            if (RB_WIDE_LDSPOS) s_didx[r * NB + tid] = slot_of(u);
+        }
+        for (int u = 0; u < np_; ++u) s_id[u * NB + tid] = (int32_t)s_cand[u * NB + tid];
+    } else if (np_ > 1) {
+        for (int u = 0; u < np_; ++u) {
+            const int32_t v = s_id[row(u)];
+            int r = 0;
+            for (int q = 0; q < np_; ++q) r += s_id[row(q)] < v ? 1 : 0;
+            s_cand[r * NB + tid] = (uint32_t)v;
+            if (RB_WIDE_LDSPOS) s_didx[r * NB + tid] = slot_of(u);
+        }
+        for (int u = 0; u < np_; ++u) s_id[u * NB + tid] = (int32_t)s_cand[u * NB + tid];
+    } else if (np_ == 1) {
+        if (na == 0) s_id[tid] = s_id[row(0)];
+        if (RB_WIDE_LDSPOS) s_didx[tid] = slot_of(0);
+    }
+    if (EP && appended && np_ > 1) {                  // equal ids are adjacent: the second is dropped
+        int32_t w = 1;
+        int32_t prev = s_id[tid];
+        for (int u = 1; u < np_; ++u) {
+            const int32_t v = s_id[u * NB + tid];
+            if (v != prev) {
+                s_id[w * NB + tid] = v;
+                if (RB_WIDE_LDSPOS) s_didx[w * NB + tid] = s_didx[u * NB + tid];
+                ++w;
+            }
+            prev = v;
+        }
+        np_ = w;
+    }
     if (overflow) atomicOr(p.err, ERR_PARTNER_OVERFLOW);
     return np_;
 }

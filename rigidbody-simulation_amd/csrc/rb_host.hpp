@@ -49,6 +49,10 @@ struct rb_world {
     // A/B steps 261-460, profiles/r03/wide_help_ab.txt): 32k 13.6 -> 12.9
     // us, C3 16.8 -> 16.1, C4 15.4 -> 14.9, C5 (16,384 cubes) 12.1 -> 9.6
     bool wide_help = true;
+    // that form with the contact search shared between its two waves: the
+    // helper lane of a body searches four of its eight buckets (rb_grid.hpp
+    // search_half_wide; RBHIP_HELP_SEARCH)
+    bool help_search = true;
     double planes[RB_MAX_PLANES][6] = {};
     double g[3] = {};
     double inv_cs = 1.0;

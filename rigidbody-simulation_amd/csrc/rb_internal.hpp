@@ -418,13 +418,14 @@ template <typename T> hipError_t launch_tile_unbin(const TileIO<T> &p, hipStream
 // lane per body at one wave per SIMD (mid-size scenes)
 enum : int { FORM_ONE = 0, FORM_COOP = 1, FORM_WIDE = 2, FORM_COOP_HELP = 3, FORM_WIDE_HELP = 4, FORM_TILE = 5 };
 // boxes: the box-capable instantiation (box-box / sphere-box narrowphase)
-template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, int form, bool boxes, hipStream_t s);
+// share: the helper-wave wide form with the search shared between its two waves
+template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, int form, bool boxes, bool share, hipStream_t s);
 // the wide form's kernels alone (rb_step_wide.hip, built with the
 // memory-clause scheduling flags).  Declared extern: that unit holds the
 // only instantiations, every other unit calls them
-template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, hipStream_t s);
-extern template hipError_t launch_step_wide<double>(const StepParams<double> &, int, bool, hipStream_t);
-extern template hipError_t launch_step_wide<float>(const StepParams<float> &, int, bool, hipStream_t);
+template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, bool share, hipStream_t s);
+extern template hipError_t launch_step_wide<double>(const StepParams<double> &, int, bool, bool, hipStream_t);
+extern template hipError_t launch_step_wide<float>(const StepParams<float> &, int, bool, bool, hipStream_t);
 template <typename T> hipError_t launch_insert(const InsertParams<T> &p, hipStream_t s);   // rb_io.hip
 // rb_set_state / rb_get_state on the device: the reference's AoS rows (qpos
 // stride 7: x y z qw qx qy qz; qvel stride 6: v, w; multi_sphere_bounce.py:85-88)

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(STEP_BLOCK) void update_kernel(StepParams<T> p) {
     }
 }
 
-template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, int form, bool boxes, hipStream_t s) {
+template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, int form, bool boxes, bool share, hipStream_t s) {
     const bool coop = form == FORM_COOP || form == FORM_COOP_HELP;
     const int nb = coop ? STEP_BLOCK / 8 : STEP_BLOCK;
     int64_t blocks = (p.n_local + nb - 1) / nb;
@@ -180,7 +180,7 @@ template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, i
         if (maxp <= 16) hipLaunchKernelGGL((step_kernel_coop<T, 16>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
         else hipLaunchKernelGGL((step_kernel_coop<T, 32>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
     } else if (form == FORM_WIDE || form == FORM_WIDE_HELP) {
-        const hipError_t we = launch_step_wide<T>(p, maxp, form == FORM_WIDE_HELP, s);
+        const hipError_t we = launch_step_wide<T>(p, maxp, form == FORM_WIDE_HELP, share, s);
         if (we != hipSuccess) return we;
     } else {
         if (maxp <= 16) hipLaunchKernelGGL((step_kernel_one<T, 16>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
@@ -202,6 +202,6 @@ using Real = float;
 #else
 #error "RB_INST: 1 (fp64) or 2 (fp32)"
 #endif
-template hipError_t launch_step<Real>(const StepParams<Real> &, int, int, bool, hipStream_t);
+template hipError_t launch_step<Real>(const StepParams<Real> &, int, int, bool, bool, hipStream_t);
 
 }  // namespace rb

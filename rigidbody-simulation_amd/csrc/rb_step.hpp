@@ -40,11 +40,13 @@
         unsigned long long t_;                                                                    \
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
         __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (tid == 0 && blockIdx.x < (1u << 16)) rb_stamp_buf[blockIdx.x][k] = t_;                \
+        /* a workgroup's second wave (shared search): its own buffer */                           \
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < (1u << 16))                                   \
+            (threadIdx.x >> 6 ? rb_stamp_buf_help : rb_stamp_buf)[blockIdx.x][k] = t_;            \
         if (k == 0 || k == 6) { /* the constant-rate clock too, comparable across XCDs */            \
             unsigned long long r_;                                                                \
             asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_)::"memory");        \
-            if (tid == 0 && blockIdx.x < (1u << 16)) rb_stamp_buf[blockIdx.x][k == 0 ? 12 : 13] = r_; \
+            if (threadIdx.x == 0 && blockIdx.x < (1u << 16)) rb_stamp_buf[blockIdx.x][k == 0 ? 12 : 13] = r_; \
         }                                                                                         \
     } while (0)
 #else
@@ -514,13 +516,15 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
 // One body (G lanes): contact search, then (lane 0) the update.  WIDE: the
 // one-lane form for one wave per SIMD (search_buckets_wide; state loads and
 // inv(I_w) under the head loads).
-template <typename T, int MAXP, int G, bool WIDE, bool BOXES, bool PRE = false, bool HELP = false, bool EP = false>
+template <typename T, int MAXP, int G, bool WIDE, bool BOXES, bool PRE = false, bool HELP = false, bool EP = false,
+          bool SHARE = false>
 __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> &ld, bool active, int64_t lb, int slot,
                                           int k, int tid,
                                           int32_t *s_id, Snap<T> *s_pos, int32_t *t_id, Snap<T> *t_pos,
                                           uint32_t *s_cand, int32_t *cell, uint32_t gen, T *s_poly,
                                           uint8_t *s_didx = nullptr, Snap<T> *s_hpos = nullptr,
-                                          const T *s_help = nullptr) {
+                                          T *s_help = nullptr, int role = 0, uint32_t *s_half = nullptr) {
+    static_assert(!SHARE || (G == 1 && WIDE && HELP && !BOXES), "shared search: the helper-wave wide form");
     constexpr int NB = STEP_BLOCK / G;
     const int32_t l = active ? (int32_t)lb : 0;
     const int32_t i = ld.lo + l;
@@ -541,7 +545,15 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     // state loads issued before the search (the wide form measured 5 % slower
     // with them issued after the bucket heads, C3)
     constexpr bool early = G > 1 || WIDE;
-    if constexpr (early && HELP && WIDE) {
+    if constexpr (SHARE) {
+        // both waves run this function (role 1: the helper wave, lane t for
+        // the body of body lane t); the helper loads the state and constants
+        if (role && active) {
+            in = load_body(ld.st, ld.cs, l, i);
+            invI.I = in.I;
+            invI.q = in.q;
+        }
+    } else if constexpr (early && HELP && WIDE) {
         // the helper wave loads the state and constants (help_body) and hands
         // over q, m, inv(I_w) and the post-gravity, post-plane v and w: the
         // body lanes load only what the search needs (the cooperative form
@@ -594,7 +606,50 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     STAMP(1);
     int32_t np_ = 0;
     bool defer = false;                          // a box-involved partner in range: the box kernel steps it
-    if constexpr (G == 1 && WIDE && HELP) {
+    [[maybe_unused]] int32_t n_half = 0;         // shared search: this wave's hits
+    if constexpr (SHARE) {
+        // the search shared with the helper wave (rb_grid.hpp
+        // search_half_wide): each wave four of the eight buckets.  The helper
+        // does its work (help_body's: inv(I_w), gravity, plane contacts)
+        // under its head loads and keeps the results in registers until the
+        // body wave is done with the list area
+        M3<T> hm{};
+        int32_t hrec = 0;
+        bool hplanes = false;
+        if (RB_ABLATE != 1 && active)
+            n_half = search_half_wide<T, MAXP, EP>(
+                p, i, x, role, s_id, s_cand, s_hpos, tid, gen, cur, b0,
+                [&](uint32_t tj, const Snap<T> &s) { return candidate_hit<T, BOXES>(p, i, kind, x, sz.x, bi, tj, s, defer); },
+                [&] {
+                    if (!role) return;
+                    hm = invI.get();
+                    if (!p.xfrc) {
+                        apply_force(p, l, in.m, invI, in.v, in.w);
+                        const T hk = impulse_k(in.m);
+                        if (kind == 0) solve_planes_sphere(p, p, l, x, sz.x, in.m, hk, invI, in.v, in.w, hrec);
+                        else solve_planes_box(p, p, l, x, mj_body_mat(in.q), sz, in.m, hk, invI, in.v, in.w, hrec);
+                        hplanes = true;
+                    }
+                });
+        if (role && active) s_half[tid] = (uint32_t)(n_half < 0xffff ? n_half : 0xffff) | (defer ? 1u << 16 : 0u);
+#if RB_STAMPS
+        if (role) STAMP(2);                      // the helper's last hit is written
+#endif
+        __syncthreads();                         // both searches are done with s_cand: the helper fills it
+        if (role && active) {
+            T *o = s_help + tid;
+#pragma unroll
+            for (int e = 0; e < 9; ++e) o[e * NB] = hm.a[e];
+            o[9 * NB] = in.v.x; o[10 * NB] = in.v.y; o[11 * NB] = in.v.z;
+            o[12 * NB] = in.w.x; o[13 * NB] = in.w.y; o[14 * NB] = in.w.z;
+            o[15 * NB] = T(hplanes ? hrec : -1);
+            o[16 * NB] = in.q.w; o[17 * NB] = in.q.x; o[18 * NB] = in.q.y; o[19 * NB] = in.q.z;
+            o[20 * NB] = in.m;
+        }
+        __syncthreads();
+        if (role) return;
+        if (active) defer |= (s_half[tid] >> 16) != 0;
+    } else if constexpr (G == 1 && WIDE && HELP) {
         // the helper wave evaluates inv(I_w), gravity and the plane contacts
         // (help_body); every lane of the body wave takes part in its two
         // barriers, so the search runs under the active mask only
@@ -670,6 +725,17 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         const T pr = o[15 * NBH];
         help_planes = pr >= T(0);
         help_nrec = help_planes ? (int32_t)pr : 0;
+    }
+    // shared search: the two halves' hits, merged and ordered (its scratch is
+    // the list area, so after the helper's results are read from it)
+    if constexpr (SHARE) {
+        // the results above were read through a T pointer from the area the
+        // merge now writes as uint32 rows: no access may move across this point
+        asm volatile("" ::: "memory");
+        if (RB_ABLATE != 1)
+            np_ = merge_halves<T, MAXP, EP>(p, s_id, s_cand, s_didx, tid, n_half, (int32_t)(s_half[tid] & 0xffffu), ep_appended);
+        STAMP(7);
+        if (RB_ABLATE == 7) np_ = 0;
     }
     constexpr int PM = G > 1 ? 1 : (WIDE && RB_WIDE_LDSPOS) ? 2 : 0;
     constexpr int SD = (WIDE && HELP) ? RB_SOLVE_DEPTH : 1;
@@ -776,8 +842,10 @@ __device__ __forceinline__ void help_body(const StepParams<T> &p, const Lead<T> 
 // HALO: the halo push compiled in (checked at run time: p.halo.mail); the
 // wide forms — the single-GPU bench's kernels — are also instantiated
 // without it (launch_step_wide picks), which measured 1-2 % faster at C3
+// SHARE: the helper wave of the wide form also searches half of each body's
+// neighbourhood (body_step; rb_grid.hpp search_half_wide)
 template <typename T, int MAXP, int G, bool WIDE = false, bool BOXES = false, bool HELP = false, bool HALO = true,
-          bool EP = false>
+          bool EP = false, bool SHARE = false>
 __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> &ld) {
     constexpr int NB = STEP_BLOCK / G;          // bodies per workgroup
     __shared__ int32_t s_id[MAXP * NB];
@@ -792,9 +860,13 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     __shared__ T s_help[HELP && !WIDE ? HELP_REALS * NB : 1];
     static_assert(!WIDE || sizeof(uint32_t) * WIDE_MAXC >= HELP_REALS * sizeof(T), "helper results fit in s_cand");
     T *const help_lds = WIDE ? reinterpret_cast<T *>(s_cand) : s_help;
-    const int tid = threadIdx.x;
+    // shared search: the helper's hit count and defer flag, per body
+    __shared__ uint32_t s_half[SHARE ? NB : 1];
+    // (wave-uniform: the second wave of a SHARE workgroup runs body_step too)
+    const int role = SHARE ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / STEP_BLOCK)) : 0;
+    const int tid = SHARE ? (int)(threadIdx.x % STEP_BLOCK) : (int)threadIdx.x;
     if (RB_ABLATE == 3) return;
-    if constexpr (HELP) {
+    if constexpr (HELP && !SHARE) {
         static_assert(!BOXES, "helper waves: the sphere step kernels");
         if (tid >= STEP_BLOCK) {                 // the workgroup's second wave
             help_body<T, NB, WIDE>(p, ld, tid - STEP_BLOCK, help_lds);
@@ -804,7 +876,7 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     STAMP(0);
 #if RB_STAMPS
     // placement: HW_ID (wave, SIMD, CU, SE fields) and XCC_ID of the block's first wave
-    if (tid == 0 && blockIdx.x < (1u << 16)) {
+    if (threadIdx.x == 0 && blockIdx.x < (1u << 16)) {
         rb_stamp_buf[blockIdx.x][15] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
         rb_stamp_buf[blockIdx.x][14] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
     }
@@ -822,8 +894,10 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     const bool active = lb < ld.n_local;
     int32_t cell[6] = {INT32_MAX, 0, 0, 0, 0, 0};   // new cell, step-start cell (peer-to-peer exchange)
     if (G > 1 || HELP || active)                 // (a helper's barriers: every lane)
-        body_step<T, MAXP, G, WIDE, BOXES, true, HELP, EP>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos, s_cand,
-                                                       cell, 0u /* loaded in body_step */, s_poly, s_didx, s_hpos, help_lds);
+        body_step<T, MAXP, G, WIDE, BOXES, true, HELP, EP, SHARE>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos,
+                                                              s_cand, cell, 0u /* loaded in body_step */, s_poly, s_didx,
+                                                              s_hpos, help_lds, role, s_half);
+    if (SHARE && role) return;                   // the helper wave is done
     if (p.bounds) fold_bounds(p.bounds, cell);
     if (HALO && p.halo.mail) {                   // halo-exchanging shard: push to the peers
         int32_t b[6];

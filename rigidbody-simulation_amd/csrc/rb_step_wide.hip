@@ -17,12 +17,16 @@
 #endif
 #if RB_STAMPS
 __device__ unsigned long long rb_stamp_buf[1 << 16][16];
+__device__ unsigned long long rb_stamp_buf_help[1 << 16][16];   // the helper wave's (shared search)
 #endif
 #include "rb_step.hpp"
 
 #if RB_STAMPS
 extern "C" int rb_diag_stamps(unsigned long long *out, int nblocks) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rb_stamp_buf), sizeof(unsigned long long) * 16 * nblocks);
+}
+extern "C" int rb_diag_stamps_help(unsigned long long *out, int nblocks) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rb_stamp_buf_help), sizeof(unsigned long long) * 16 * nblocks);
 }
 #endif
 
@@ -39,15 +43,17 @@ void step_kernel_wide(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T
 
 // the wide form with a helper wave per workgroup (help_body): two waves per
 // SIMD, each within 256 registers
-template <typename T, int MAXP, bool HALO, bool EP>
+// SHARE: the helper lanes also search half of each body's 2x2x2
+// neighbourhood (rb_grid.hpp search_half_wide)
+template <typename T, int MAXP, bool HALO, bool EP, bool SHARE>
 __global__ __launch_bounds__(2 * STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void step_kernel_wide_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
                            const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, true, HALO, EP>(
+    step_body<T, MAXP, 1, true, false, true, HALO, EP, SHARE>(
         p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
 }
 
-template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, hipStream_t s) {
+template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, bool share, hipStream_t s) {
     int64_t blocks = (p.n_local + STEP_BLOCK - 1) / STEP_BLOCK;
     if (blocks < 1) blocks = 1;
     const bool halo = p.halo.mail != nullptr;
@@ -56,6 +62,11 @@ template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int ma
     const bool ep = p.ep.ctrl != nullptr && !halo;
 #define RB_WIDE_LAUNCH(K, M, H, E, TH)                                                                            \
     hipLaunchKernelGGL((K<T, M, H, E>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p)
+#define RB_WIDE_HELP_LAUNCH(M, H, E, TH)                                                                          \
+    do {                                                                                                          \
+        if (share) hipLaunchKernelGGL((step_kernel_wide_help<T, M, H, E, true>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p); \
+        else hipLaunchKernelGGL((step_kernel_wide_help<T, M, H, E, false>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p); \
+    } while (0)
 #define RB_WIDE_PICK(K, M, TH)                                                                                    \
     do {                                                                                                          \
         if (halo) RB_WIDE_LAUNCH(K, M, true, false, TH);                                                          \
@@ -63,8 +74,16 @@ template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int ma
         else RB_WIDE_LAUNCH(K, M, false, false, TH);                                                              \
     } while (0)
     if (help) {
-        if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide_help, 16, 2 * STEP_BLOCK);
-        else RB_WIDE_PICK(step_kernel_wide_help, 32, 2 * STEP_BLOCK);
+#define RB_WIDE_HELP_PICK(M)                                                                                      \
+    do {                                                                                                          \
+        if (halo) RB_WIDE_HELP_LAUNCH(M, true, false, 2 * STEP_BLOCK);                                            \
+        else if (ep) RB_WIDE_HELP_LAUNCH(M, false, true, 2 * STEP_BLOCK);                                         \
+        else RB_WIDE_HELP_LAUNCH(M, false, false, 2 * STEP_BLOCK);                                                \
+    } while (0)
+        if (maxp <= 16) RB_WIDE_HELP_PICK(16);
+        else RB_WIDE_HELP_PICK(32);
+#undef RB_WIDE_HELP_PICK
+#undef RB_WIDE_HELP_LAUNCH
         return hipGetLastError();
     }
     if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide, 16, STEP_BLOCK);
@@ -81,6 +100,6 @@ using Real = float;
 #else
 #error "RB_INST: 1 (fp64) or 2 (fp32)"
 #endif
-template hipError_t launch_step_wide<Real>(const StepParams<Real> &, int, bool, hipStream_t);
+template hipError_t launch_step_wide<Real>(const StepParams<Real> &, int, bool, bool, hipStream_t);
 
 }  // namespace rb

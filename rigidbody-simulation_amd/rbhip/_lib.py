@@ -92,7 +92,7 @@ SIGNATURES = {
 STAT_NAMES = ["graphs", "form", "box_opt_chunks", "box_rollbacks", "refits", "table_grows", "buckets",
               "max_partners", "io_skipped", "io_uploads", "tile_runs", "tile_steps", "tile_rollbacks",
               "tile_builds", "tile_why", "tile_slots", "tile_cols", "tile_on", "hashed_form",
-              "append_steps", "rebuild_steps", "table_epoch"]
+              "append_steps", "rebuild_steps", "table_epoch", "grid_layout", "help_search"]
 FORM_NAMES = {0: "rb::step_kernel_one", 1: "rb::step_kernel_coop", 2: "rb::step_kernel_wide",
               3: "rb::step_kernel_coop_help", 4: "rb::step_kernel_wide_help", 5: "rb::tile_step_kernel"}
 

@@ -1,7 +1,11 @@
 """Diagnostic: per-phase cycle stamps of the step kernel (RB_STAMPS build).
 Phases: 0 start | 1 after table clear | 2 after broadphase search |
 3 after state load + gravity | 4 after contact solves | 5 after position
-store + insert | 6 end.  Prints the median / p90 over workgroups."""
+store + insert | 6 end.  Prints the median / p90 over workgroups.
+Shared search (the wide + helper form, RBHIP_HELP_SEARCH=1): the body wave's
+stamp 2 is taken after the barriers (its search span: 1 -> 10), 7 after the
+merge and sort; the helper wave's stamps (its own buffer) are 0 start |
+1, 8, 9, 10 as the body wave's | 2 its last hit written."""
 import ctypes, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,6 +21,23 @@ from rbhip import _lib, scenes
 import rbhip.world as W
 L = _lib.load(LIB)
 L.rb_diag_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
+def report_help(kind, buf, hbuf):
+    """The helper wave of the shared search, beside the body wave's search."""
+    if not hbuf[:, 2].any():
+        return
+    i64 = lambda a: a.astype(np.int64)            # noqa: E731
+    body = i64(buf[:, 10]) - i64(buf[:, 1])
+    span = i64(hbuf[:, 2]) - i64(hbuf[:, 0])
+    late = i64(hbuf[:, 2]) - i64(buf[:, 10])
+    print(f"   [{kind}] body wave search (1 -> 10) median {int(np.median(body))} p90 {int(np.percentile(body, 90))}; "
+          f"merge + sort (2 -> 7) median {int(np.median(i64(buf[:, 7]) - i64(buf[:, 2])))}")
+    print(f"   [{kind}] helper wave start -> last hit written median {int(np.median(span))} p90 {int(np.percentile(span, 90))}; "
+          f"helper done after the body wave's search by median {int(np.median(late))} p90 {int(np.percentile(late, 90))}")
+    for a, b_, nm in [(0, 1, "lead"), (1, 8, "snap+heads+work"), (8, 9, "heads+batch1"), (9, 10, "later batches")]:
+        dd = i64(hbuf[:, b_]) - i64(hbuf[:, a])
+        print(f"     helper {nm:16s} median {int(np.median(dd)):8d}  p90 {int(np.percentile(dd, 90)):8d}")
+
+
 def report(sc, G, kind, buf):
     d = np.diff(buf[:, :7].astype(np.int64), axis=1)
     tot = (buf[:, 6].astype(np.int64) - buf[:, 0].astype(np.int64))
@@ -60,8 +81,14 @@ for nx, ny, warm in sizes:
             if kind not in seen:
                 buf = np.zeros((nb, 16), np.uint64)
                 L.rb_diag_stamps(buf.ctypes.data_as(ctypes.c_void_p), nb)
-                seen[kind] = buf
+                hbuf = np.zeros((nb, 16), np.uint64)
+                if hasattr(L, "rb_diag_stamps_help"):
+                    L.rb_diag_stamps_help.argtypes = [ctypes.c_void_p, ctypes.c_int]
+                    L.rb_diag_stamps_help(hbuf.ctypes.data_as(ctypes.c_void_p), nb)
+                seen[kind] = (buf, hbuf)
             if kind == "step" or len(seen) == 2:
                 break
-    for kind, buf in seen.items():
+    for kind, (buf, hbuf) in seen.items():
         report(sc, G, kind, buf)
+        if G == 1:
+            report_help(kind, buf, hbuf)
