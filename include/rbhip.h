@@ -338,16 +338,19 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
 /* Many small independent scenes ("environments") stepped by one launch: a
  * parameter sweep, an ensemble of initial conditions, a domain-randomised
  * batch of the reference's scenes (1 to 4 bodies each).  A batch is n_envs
- * replicas of a template environment of M = n_bodies <= 64 bodies; planes,
- * gravity, dt, the contact threshold and the normal convention are per
- * batch, restitution / friction / body constants / state per environment.
+ * replicas of a template environment of M = n_bodies <= 64 bodies; the
+ * plane count, dt, the contact threshold and the normal convention are per
+ * batch; restitution / friction / body constants / state and, additive to
+ * 0.4 (rb_version is unchanged), the planes' values, gravity and applied
+ * forces (rb_batch_set_planes / _gravity / _xfrc) are per environment.
  * An environment steps bit-identically to an rb_world of the same scene,
  * under either contact law (rb_batch_set_contact_law).
  * Arrays are environment-major: body k of environment e at row e*M + k.
- * Not covered (use rb_world): applied forces, contact recording, caller
- * streams and asynchronous stepping, sharding, box-involved pairs (a box is
- * accepted only as the single body of its environment),
- * per-environment planes or gravity, more than 64 bodies per environment.
+ * Not covered (use rb_world): contact recording, caller streams and
+ * asynchronous stepping, sharding, box-involved pairs (a box is accepted
+ * only as the single body of its environment), per-environment plane
+ * counts, more than 64 bodies per environment; under RB_LAW_BALLS also
+ * per-environment planes and applied forces.
  * A batch handle is not thread-safe; every call is synchronous.
  *
  * A step launch runs at most RB_BATCH_CHUNK steps (a bound on kernel duration
@@ -436,6 +439,34 @@ int  rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol);
 int  rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, double restitution,
                           double friction, double contact_threshold, double *qpos, double *qvel,
                           int64_t *n_failed);
+/* Per-environment planes, gravity and applied forces (additive to librbhip
+ * 0.4).  Each call is synchronous; the values persist across steps and
+ * across rb_batch_set_state (a reset does not touch them) and are converted
+ * to the batch's real type as the template's are.  A non-finite value is
+ * RB_EINVAL (the message names the environment, and the plane or body); a
+ * refused call changes nothing.  While any of the three is set, steps and
+ * sampled runs launch the per-environment instances of the step kernels;
+ * failure semantics (rb_batch_step) are the same.
+ *
+ * planes [n_envs][n_planes][6] (normal xyz, point xyz), n_planes = the
+ * template's; NULL = every environment uses the template's planes again.
+ * RB_EINVAL for a non-NULL array when the template has no plane.  Replaces
+ * the model's plane rewritten from INCLINE_ANGLE_RAD (cube_incline.py:28-34;
+ * sim_overrides.py), one model per angle. */
+int  rb_batch_set_planes(rb_batch *b, const double *planes);
+/* gravity [n_envs][3]; NULL = the template's.  Replaces model.opt.gravity of
+ * a per-variant model (collision.py:66; ball_collision.py:78).  Honoured
+ * under both contact laws. */
+int  rb_batch_set_gravity(rb_batch *b, const double *gravity);
+/* xfrc [n_envs*M][6] (force xyz, torque xyz) as rb_set_xfrc; NULL = none.
+ * Replaces data.xfrc_applied (collision.py:66-70).  While set, every body of
+ * every environment takes the applied-force path of the step, all-zero rows
+ * included (which matters for the sign of zeros), as a world with rb_set_xfrc
+ * does.
+ * Under RB_LAW_BALLS rb_batch_set_planes and rb_batch_set_xfrc with a non-NULL
+ * array, and rb_batch_set_contact_law(RB_LAW_BALLS) while either is set,
+ * return RB_EUNSUPPORTED and change nothing. */
+int  rb_batch_set_xfrc(rb_batch *b, const double *xfrc);
 
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do

@@ -2,6 +2,8 @@
 // E replicas of a template environment of M <= 64 bodies, body b of
 // environment e at slot e * M + b of every device row.  All work is enqueued
 // on the batch's own stream; every entry point returns after it finished.
+#include <cmath>
+
 #include "rb_host.hpp"
 #include "rb_sampleplan.hpp"
 
@@ -22,6 +24,11 @@ struct rb_batch {
     void *snap = nullptr, *state = nullptr, *consts = nullptr;
     void *env_e = nullptr, *env_mu = nullptr;   // [E] reals; used while have_*
     bool have_e = false, have_mu = false;
+    // per-environment planes [n_planes][6][E], gravity [3][E] and applied
+    // forces [6][E * M] (reals; allocated by the first call that sets them,
+    // used while have_*): any of them selects the ENVS step instances
+    void *env_planes = nullptr, *env_g = nullptr, *env_xfrc = nullptr;
+    bool have_planes = false, have_g = false, have_xfrc = false;
     int32_t *code = nullptr, *count = nullptr;
     int64_t *steps_done = nullptr;
     double *io_q = nullptr, *io_v = nullptr;    // device staging of the AoS rows
@@ -47,7 +54,7 @@ void free_batch(rb_batch *b) {
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids, b->samp};
+                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -86,6 +93,35 @@ int batch_put_row(rb_batch *b, int row, const double *src, int stride, int off) 
     });
 }
 
+// A per-environment array into its device rows (rb_batch_set_planes / _gravity
+// / _xfrc): src is [units][width] doubles, the device copy `width` rows of
+// `units` reals (struct-of-arrays, as the batch's real type), allocated on
+// first use.  Nothing of the batch changes unless every step succeeds.
+int batch_put_env(rb_batch *b, void **buf, bool *have, const double *src, int64_t units, int width) {
+    HIPCHK(hipSetDevice(b->device));
+    if (!src) {
+        *have = false;
+        return RB_OK;
+    }
+    const size_t n = (size_t)units * (size_t)width;
+    void *dst = *buf;
+    if (!dst) HIPCHK(hipMalloc(&dst, n * (size_t)b->esz));
+    const int rc = by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        std::vector<T> h(n);
+        for (int64_t u = 0; u < units; ++u)
+            for (int d = 0; d < width; ++d) h[(size_t)d * (size_t)units + (size_t)u] = (T)src[(size_t)u * width + d];
+        return bput(b, dst, h.data(), sizeof(T) * n);
+    });
+    if (rc != RB_OK) {
+        if (!*buf) (void)hipFree(dst);
+        return rc;
+    }
+    *buf = dst;
+    *have = true;
+    return RB_OK;
+}
+
 template <typename T> StateIO<T> batch_io(rb_batch *b) {
     StateIO<T> p{};
     p.qpos = b->io_q;
@@ -122,6 +158,9 @@ template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double
     p.inv_cs = (T)b->inv_cs;
     p.tol = (T)b->tol;
     p.ground = b->n_planes == 1;
+    p.env_planes = b->have_planes ? dp<T>(b->env_planes, 0) : nullptr;
+    p.env_g = b->have_g ? dp<T>(b->env_g, 0) : nullptr;
+    p.env_xfrc = b->have_xfrc ? dp<T>(b->env_xfrc, 0) : nullptr;
     return p;
 }
 
@@ -369,6 +408,9 @@ int rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol) {
         const double ground[6] = {0, 0, 1, 0, 0, 0};
         if (b->n_planes > 1 || (b->n_planes == 1 && memcmp(b->planes[0], ground, sizeof(ground)) != 0))
             return fail(RB_EUNSUPPORTED, "the two-ball law's only plane is the z = 0 ground (ball_collision.py:88-90)");
+        if (b->have_planes || b->have_xfrc)
+            return fail(RB_EUNSUPPORTED, "the two-ball law takes no per-environment planes or applied forces "
+                                         "(clear them first: rb_batch_set_planes / rb_batch_set_xfrc with NULL)");
     }
     // both laws keep a ball's true position in the snapshots and neither
     // caches anything between launches: a switch converts nothing
@@ -376,6 +418,49 @@ int rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol) {
     b->tol = tol;
     batch_set_cell(b);
     return RB_OK;
+}
+
+int rb_batch_set_planes(rb_batch *b, const double *planes) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (planes) {
+        if (b->n_planes == 0) return fail(RB_EINVAL, "the template has no plane: the plane count is the template's");
+        for (int64_t e = 0; e < b->E; ++e)
+            for (int k = 0; k < b->n_planes; ++k)
+                for (int j = 0; j < 6; ++j)
+                    if (!std::isfinite(planes[((size_t)e * b->n_planes + k) * 6 + j]))
+                        return fail(RB_EINVAL, "environment %lld, plane %d: non-finite value", (long long)e, k);
+        if (b->law == RB_LAW_BALLS)
+            return fail(RB_EUNSUPPORTED, "the two-ball law's only plane is the z = 0 ground: no per-environment planes");
+    }
+    // [E][n_planes * 6] -> n_planes * 6 rows of E
+    return batch_put_env(b, &b->env_planes, &b->have_planes, planes, b->E, b->n_planes * 6);
+}
+
+int rb_batch_set_gravity(rb_batch *b, const double *gravity) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (gravity)
+        for (int64_t e = 0; e < b->E; ++e)
+            for (int j = 0; j < 3; ++j)
+                if (!std::isfinite(gravity[3 * e + j]))
+                    return fail(RB_EINVAL, "environment %lld: non-finite gravity", (long long)e);
+    return batch_put_env(b, &b->env_g, &b->have_g, gravity, b->E, 3);
+}
+
+int rb_batch_set_xfrc(rb_batch *b, const double *xfrc) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (xfrc) {
+        for (int64_t g = 0; g < b->N; ++g)
+            for (int j = 0; j < 6; ++j)
+                if (!std::isfinite(xfrc[6 * g + j]))
+                    return fail(RB_EINVAL, "environment %lld, body %lld: non-finite applied force or torque",
+                                (long long)(g / b->M), (long long)(g % b->M));
+        if (b->law == RB_LAW_BALLS)
+            return fail(RB_EUNSUPPORTED, "the two-ball law takes no applied forces (ball_collision.py:73-125)");
+    }
+    return batch_put_env(b, &b->env_xfrc, &b->have_xfrc, xfrc, b->N, 6);
 }
 
 int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr, int64_t *n_failed) {

@@ -43,9 +43,39 @@ __device__ __forceinline__ void sample_store(const BatchParams<T> &p, int32_t sl
     }
 }
 
+// The dynamic LDS of the ENVS instances: the planes of the wave's environments
+// (one declaration for both real types, hence bytes)
+extern __shared__ __align__(16) unsigned char s_env_dyn[];
+
+// The wave's block of per-environment planes, [plane][component][environment
+// of the wave] (EnvPlanes, rb_internal.hpp), filled once per launch: from the
+// batch's rows, or with the template's planes where no rows are set, so a step
+// reads its planes one way.  Lane el < epw fills environment el of the wave.
+template <typename T> __device__ __forceinline__ void env_planes_fill(const BatchParams<T> &p, T *blk, int lane, int epw) {
+    const int64_t env = (int64_t)blockIdx.x * epw + lane;
+    const bool mine = lane < epw;
+    const bool live = mine && env < p.E;             // (the rows of environments past the batch are never read)
+    for (int a = 0; a < p.n_planes; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            T n = p.pn[a][c], o = p.pp[a][c];
+            if (p.env_planes) {
+                n = live ? p.env_planes[((int64_t)a * 6 + c) * p.E + env] : T(0);
+                o = live ? p.env_planes[((int64_t)a * 6 + 3 + c) * p.E + env] : T(0);
+            }
+            if (mine) {
+                blk[(a * 6 + c) * epw + lane] = n;
+                blk[(a * 6 + 3 + c) * epw + lane] = o;
+            }
+        }
+    }
+}
+
 // BOX: the template environment is one box (M == 1); else spheres only
 // REC: the recording instance of a sampled run
-template <typename T, bool BOX, bool REC>
+// ENVS: per-environment planes, gravity or applied forces are set (each of
+// the three optional: a null pointer means the batch's)
+template <typename T, bool BOX, bool REC, bool ENVS>
 __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> p) {
     __shared__ Snap<T> s_snap[2][BATCH_BLOCK];
     __shared__ int32_t s_fail[BATCH_BLOCK];      // per environment of the wave; sticky within a launch
@@ -90,6 +120,23 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
     sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
     sp.oriented = p.oriented;
 
+    // ---- ENVS: the environment's gravity and planes, the body's applied force
+    V3<T> xf = {T(0), T(0), T(0)}, xt = xf;
+    EnvPlanes<T> epl{};
+    if constexpr (ENVS) {
+        if (p.env_g) { sp.g[0] = p.env_g[ev]; sp.g[1] = p.env_g[p.E + ev]; sp.g[2] = p.env_g[2 * p.E + ev]; }
+        if (p.env_xfrc) {
+            const int64_t N = p.E * M;
+            xf = {p.env_xfrc[g], p.env_xfrc[N + g], p.env_xfrc[2 * N + g]};
+            xt = {p.env_xfrc[3 * N + g], p.env_xfrc[4 * N + g], p.env_xfrc[5 * N + g]};
+        }
+        T *blk = reinterpret_cast<T *>(s_env_dyn);
+        env_planes_fill(p, blk, lane, epw);          // (visible after the barrier below)
+        epl.n_planes = p.n_planes;
+        epl.pn = {blk + el, epw};
+        epl.pp = {blk + 3 * epw + el, epw};
+    }
+
     s_fail[lane] = 0;
     s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
     __syncthreads();
@@ -106,14 +153,22 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
         LazyInvI<T> invI;
         invI.I = I;
         invI.q = q;
-        // ---- a4: gravity (collision.py:66-70; no applied forces here) -------
-        apply_force<T, false>(sp, 0, m, invI, vn, wn);
+        // ---- a4: gravity (collision.py:66-70); ENVS with forces set: every
+        // body takes the applied-force path, all-zero rows included ----------
+        if (ENVS && p.env_xfrc) apply_force(sp, m, invI, vn, wn, xf, xt);
+        else apply_force<T, false>(sp, 0, m, invI, vn, wn);
         const T kk = impulse_k(m);
 
-        // ---- K2: plane contacts, plane order (the planes: the batch's) -------
+        // ---- K2: plane contacts, plane order (the planes: the batch's, or
+        // ENVS: the environment's, from LDS) ----------------------------------
         int32_t nrec = 0;                        // (sp.rec_count is null: nothing is recorded)
-        if constexpr (!BOX) solve_planes_sphere(sp, p, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-        else solve_planes_box(sp, p, 0, x, mj_body_mat(q), sz, m, kk, invI, vn, wn, nrec);
+        if constexpr (ENVS) {
+            if constexpr (!BOX) solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
+            else solve_planes_box(sp, epl, 0, x, mj_body_mat(q), sz, m, kk, invI, vn, wn, nrec);
+        } else {
+            if constexpr (!BOX) solve_planes_sphere(sp, p, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
+            else solve_planes_box(sp, p, 0, x, mj_body_mat(q), sz, m, kk, invI, vn, wn, nrec);
+        }
 
         // ---- K2: every other body of the environment, ascending id ----------
         if constexpr (!BOX) {
@@ -180,7 +235,9 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
 // step's ground phase.  Nothing survives a launch but the true state: the
 // first ground phase is run from it, so dt, e and mu may change between calls.
 // The quaternion is never touched (REC loads it to record it).
-template <typename T, bool REC>
+// ENVS: per-environment gravity is set (the law takes neither per-environment
+// planes nor applied forces)
+template <typename T, bool REC, bool ENVS>
 __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T> p) {
     __shared__ Snap<T> s_snap[2][BATCH_BLOCK];
     __shared__ Vel<T> s_vel[2][BATCH_BLOCK];
@@ -219,6 +276,8 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
     sp.e = p.env_e ? p.env_e[ev] : p.e;
     sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
     sp.ground = p.ground;
+    if constexpr (ENVS)
+        if (p.env_g) { sp.g[0] = p.env_g[ev]; sp.g[1] = p.env_g[p.E + ev]; sp.g[2] = p.env_g[2 * p.E + ev]; }
     const T tol = p.tol;
 
     // the first step's ground phase, from the true state
@@ -396,20 +455,38 @@ static unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, bool balls, bool rec, hipStream_t s) {
     if (p.E <= 0 || p.k <= 0) return hipSuccess;
     if (balls && box) return hipErrorInvalidValue;
+    if (p.M < 1 || p.M > BATCH_BLOCK || p.n_planes < 0 || p.n_planes > MAX_PLANES) return hipErrorInvalidValue;
     if (rec && (!p.samp || p.every < 1 || p.phase < 1 || p.phase > p.every || (p.samp_rows != 7 && p.samp_rows != 13)))
         return hipErrorInvalidValue;
     const int64_t epw = BATCH_BLOCK / p.M;
     const unsigned blocks = (unsigned)((p.E + epw - 1) / epw);
     const dim3 gr(blocks), bl(BATCH_BLOCK);
+    // the ENVS instances: only with a per-environment array set
     if (balls) {
-        if (rec) hipLaunchKernelGGL((batch_balls_kernel<T, true>), gr, bl, 0, s, p);
-        else hipLaunchKernelGGL((batch_balls_kernel<T, false>), gr, bl, 0, s, p);
+        if (p.env_planes || p.env_xfrc) return hipErrorInvalidValue;    // (refused by the setters under this law)
+        if (p.env_g) {
+            if (rec) hipLaunchKernelGGL((batch_balls_kernel<T, true, true>), gr, bl, 0, s, p);
+            else hipLaunchKernelGGL((batch_balls_kernel<T, false, true>), gr, bl, 0, s, p);
+        } else {
+            if (rec) hipLaunchKernelGGL((batch_balls_kernel<T, true, false>), gr, bl, 0, s, p);
+            else hipLaunchKernelGGL((batch_balls_kernel<T, false, false>), gr, bl, 0, s, p);
+        }
+    } else if (p.env_planes || p.env_g || p.env_xfrc) {
+        // the wave's planes in LDS: [n_planes][6][environments per wave]
+        const size_t lds = (size_t)epw * (size_t)p.n_planes * 6 * sizeof(T);
+        if (rec) {
+            if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, true, true>), gr, bl, lds, s, p);
+            else hipLaunchKernelGGL((batch_step_kernel<T, false, true, true>), gr, bl, lds, s, p);
+        } else {
+            if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, false, true>), gr, bl, lds, s, p);
+            else hipLaunchKernelGGL((batch_step_kernel<T, false, false, true>), gr, bl, lds, s, p);
+        }
     } else if (rec) {
-        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, true>), gr, bl, 0, s, p);
-        else hipLaunchKernelGGL((batch_step_kernel<T, false, true>), gr, bl, 0, s, p);
+        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, true, false>), gr, bl, 0, s, p);
+        else hipLaunchKernelGGL((batch_step_kernel<T, false, true, false>), gr, bl, 0, s, p);
     } else {
-        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, false>), gr, bl, 0, s, p);
-        else hipLaunchKernelGGL((batch_step_kernel<T, false, false>), gr, bl, 0, s, p);
+        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, false, false>), gr, bl, 0, s, p);
+        else hipLaunchKernelGGL((batch_step_kernel<T, false, false, false>), gr, bl, 0, s, p);
     }
     return hipGetLastError();
 }

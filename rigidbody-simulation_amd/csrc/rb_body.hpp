@@ -80,6 +80,19 @@ __device__ __forceinline__ void apply_force(const StepParams<T> &p, int32_t l, T
         w = {w.x + dw.x, w.y + dw.y, w.z + dw.z};
     }
 }
+// a4 with the body's applied force xf and torque xt given by value (a caller
+// that holds them in registers: the batched worlds): the XFRC path above, in
+// its order, all-zero rows included
+template <typename T>
+__device__ __forceinline__ void apply_force(const StepParams<T> &p, T m, LazyInvI<T> &invI, V3<T> &v, V3<T> &w,
+                                            V3<T> xf, V3<T> xt) {
+    V3<T> F = {m * p.g[0], m * p.g[1], m * p.g[2]};
+    F = {xf.x + F.x, xf.y + F.y, xf.z + F.z};
+    v = {v.x + (F.x / m) * p.dt, v.y + (F.y / m) * p.dt, v.z + (F.z / m) * p.dt};
+    const V3<T> tdt = {xt.x * p.dt, xt.y * p.dt, xt.z * p.dt};
+    const V3<T> dw = np_matvec(invI.get(), tdt);
+    w = {w.x + dw.x, w.y + dw.y, w.z + dw.z};
+}
 
 // K2, a body's plane contacts, the first in its contact order: plane order,
 // a sphere's one per plane, a box's corners (8, at most 4 per plane).

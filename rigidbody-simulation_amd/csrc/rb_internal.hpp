@@ -490,9 +490,35 @@ template <typename T> struct BatchParams {
     int32_t every, phase;                // the sampling period; this launch's step `phase` (1-based) is its first sample
     int32_t samp_first, samp_slots;      // first slot of this launch; slots the buffer has
     int32_t samp_rows;                   // 7, or 13 with velocities
+    // per-environment planes, gravity and applied forces (the ENVS instances
+    // only; each nullptr: the batch's planes / gravity above, no applied force)
+    const T *env_planes;                 // [n_planes][6][E]: component-major (normal xyz, point xyz)
+    const T *env_g;                      // [3][E]
+    const T *env_xfrc;                   // [6][E * M] (force xyz, torque xyz), rows like the state's
+};
+// The planes of the environments of one wave, in LDS (batch_step_kernel's ENVS
+// instances): [plane][component][environment of the wave], so the lanes of an
+// M = 1 batch read consecutive words and the lanes of one environment read one
+// word.  It has the shape the plane helpers of rb_body.hpp read (n_planes,
+// pn[a][c], pp[a][c]).
+template <typename T> struct EnvPlanes {
+    struct Vec {
+        const T *p;
+        int32_t stride;
+        __device__ __forceinline__ T operator[](int c) const { return p[c * stride]; }
+    };
+    struct Rows {
+        const T *p;                      // component 0 of plane 0, this lane's environment
+        int32_t stride;                  // environments per wave
+        __device__ __forceinline__ Vec operator[](int a) const { return Vec{p + a * 6 * stride, stride}; }
+    };
+    int32_t n_planes;
+    Rows pn, pp;
 };
 // what rb_batch_step and rb_batch_run_sampled launch: the default law's kernel
-// (spheres or the one box), or the two-ball law's; rec: the recording instance
+// (spheres or the one box), or the two-ball law's; rec: the recording instance.
+// With one of p.env_planes / env_g / env_xfrc set it is the ENVS instance,
+// whose dynamic LDS (floor(64 / M) * n_planes * 6 reals) holds the planes.
 template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, bool balls, bool rec, hipStream_t s);
 // slots [first, first + n) of the sample buffer -> the boundary's rows, in
 // double: qpos [n][E * M][7] and (rows == 13) qvel [n][E * M][6]

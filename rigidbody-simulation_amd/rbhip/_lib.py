@@ -86,6 +86,9 @@ SIGNATURES = {
     "rb_batch_status": (C.c_int, [_P, _P, _P]),
     "rb_batch_set_contact_law": (C.c_int, [_P, _I32, _D]),
     "rb_batch_run_sampled": (C.c_int, [_P, _I64, _I64, _D, _D, _D, _D, _P, _P, C.POINTER(_I64)]),
+    "rb_batch_set_planes": (C.c_int, [_P, _P]),
+    "rb_batch_set_gravity": (C.c_int, [_P, _P]),
+    "rb_batch_set_xfrc": (C.c_int, [_P, _P]),
 }
 
 # rb_world_stats indices (include/rbhip.h RB_STAT_*)

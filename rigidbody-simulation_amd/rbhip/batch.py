@@ -4,9 +4,12 @@ step chunk (rb_batch_* in include/rbhip.h).
 The reference's scenes hold 1 to 4 bodies and are studied one knob per run
 (src/config/sim_overrides.py; the velocity variants under
 data/plots/single_sphere/).  A BatchWorld is n_envs replicas of one such
-scene, each with its own restitution, friction, body constants and state;
-every environment steps bit-identically to a World of the same scene, under
-the default contact law or the two-ball law of ball_collision.py.
+scene, each with its own restitution, friction, body constants and state,
+and (set_planes / set_gravity / set_xfrc, or one Scene per environment
+through from_scenes) its own planes, gravity and applied forces: the incline
+angle of cube_incline.py, model.opt.gravity, data.xfrc_applied.  Every
+environment steps bit-identically to a World of the same scene, under the
+default contact law or the two-ball law of ball_collision.py.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
 multi_sphere_logger.py), one per environment, sampled on the device.
@@ -67,6 +70,41 @@ class BatchWorld:
                 raise
         self.set_state(np.broadcast_to(scene.qpos0, (E, M, 7)), np.broadcast_to(scene.qvel0, (E, M, 6)))
 
+    @classmethod
+    def from_scenes(cls, scenes, **kw):
+        """A batch with one environment per Scene of `scenes` (an angle sweep:
+        [scenes.cube_incline(a) for a in angles]).  The template is
+        scenes[0]; planes, gravity, restitution, friction, mass, inertia,
+        size and the initial state are taken from every scene.  The scenes
+        must agree in body count, kinds, plane count, dt, threshold and
+        normal convention (ValueError naming the first scene that does not).
+        kw: the constructor's (device, dtype, ...)."""
+        scenes = list(scenes)
+        if not scenes:
+            raise ValueError("from_scenes: no scene given")
+        t = scenes[0]
+        for k, sc in enumerate(scenes[1:], 1):
+            for what, same in (("body count", sc.n == t.n),
+                               ("body kinds", sc.n == t.n and np.array_equal(sc.kind, t.kind)),
+                               ("plane count", np.shape(sc.planes)[0] == np.shape(t.planes)[0]),
+                               ("dt", sc.dt == t.dt), ("threshold", sc.threshold == t.threshold),
+                               ("normal convention", sc.normal_convention == t.normal_convention)):
+                if not same:
+                    raise ValueError(f"from_scenes: scene {k} ({sc.name!r}) differs from scene 0 in its {what}")
+        b = cls(t, len(scenes), **kw)
+        try:
+            if np.shape(t.planes)[0]:
+                b.set_planes(np.stack([np.asarray(sc.planes, np.float64) for sc in scenes]))
+            b.set_gravity(np.stack([np.asarray(sc.gravity, np.float64) for sc in scenes]))
+            b.set_params(restitution=[sc.restitution for sc in scenes], friction=[sc.friction for sc in scenes])
+            b.set_bodies(mass=np.stack([sc.mass for sc in scenes]), inertia=np.stack([sc.inertia for sc in scenes]),
+                         size=np.stack([sc.size for sc in scenes]))
+            b.set_state(np.stack([sc.qpos0 for sc in scenes]), np.stack([sc.qvel0 for sc in scenes]))
+        except Exception:
+            b.close()
+            raise
+        return b
+
     # ---- lifetime ---------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
@@ -113,6 +151,28 @@ class BatchWorld:
         E, M = self.n_envs, self.n_bodies
         m, i, s = self._arr(mass, (E, M)), self._arr(inertia, (E, M, 3)), self._arr(size, (E, M, 3))
         _lib.check(self._L.rb_batch_set_bodies(self._h, _lib.ptr(m), _lib.ptr(i), _lib.ptr(s)), "rb_batch_set_bodies")
+
+    def set_planes(self, planes):
+        """Per-environment planes (E, P, 6): normal xyz, point xyz; P is the
+        template's plane count.  None: the template's planes again.  The
+        values persist across steps and set_state().  Not under "balls"."""
+        P = np.shape(self.scene.planes)[0]
+        a = self._arr(planes, (self.n_envs, P, 6))
+        _lib.check(self._L.rb_batch_set_planes(self._h, _lib.ptr(a)), "rb_batch_set_planes")
+
+    def set_gravity(self, gravity):
+        """Per-environment gravity (E, 3); None: the template's.  Honoured
+        under both contact laws."""
+        a = self._arr(gravity, (self.n_envs, 3))
+        _lib.check(self._L.rb_batch_set_gravity(self._h, _lib.ptr(a)), "rb_batch_set_gravity")
+
+    def set_xfrc(self, xfrc):
+        """Per-body applied force and torque (E, M, 6) as World.set_xfrc
+        (data.xfrc_applied, collision.py:66-70); None: none.  While set, every
+        body takes the applied-force path, all-zero rows included.  Not under
+        "balls"."""
+        a = self._arr(xfrc, (self.n_envs, self.n_bodies, 6))
+        _lib.check(self._L.rb_batch_set_xfrc(self._h, _lib.ptr(a)), "rb_batch_set_xfrc")
 
     # ---- state --------------------------------------------------------------
     def _envs(self, envs):

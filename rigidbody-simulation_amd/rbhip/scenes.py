@@ -98,6 +98,30 @@ def single_cube() -> Scene:
                  names=["cube"])
 
 
+def _incline_plane_at(angle: float) -> np.ndarray:
+    """The plane through the origin with the normal (0, -sin a, cos a)."""
+    return np.array([[0.0, -np.sin(angle), np.cos(angle), 0.0, 0.0, 0.0]])
+
+
+def cube_incline(angle: float = INCLINE) -> Scene:
+    """single_cube() on an incline of `angle` rad: cube_incline.py:28-34 puts
+    INCLINE_ANGLE_RAD (sim_overrides.py) into models/cube.xml, which derives
+    the plane and the cube's start orientation (euler "angle 0 0") from it.
+    cube_incline(0.7) is single_cube(); one environment of an angle sweep
+    (BatchWorld.from_scenes)."""
+    sc = single_cube()
+    qpos = sc.qpos0.copy()
+    qpos[0, 3:7] = [np.cos(angle / 2), np.sin(angle / 2), 0.0, 0.0]
+    return sc.with_(name="cube_incline", planes=_incline_plane_at(angle), qpos0=qpos)
+
+
+def sphere_incline(angle: float = 0.0) -> Scene:
+    """single_sphere() on an incline of `angle` rad (INCLINE_ANGLE_RAD of
+    single_sphere_bounce in sim_overrides.py); the sphere's start state is
+    unchanged."""
+    return single_sphere().with_(name="sphere_incline", planes=_incline_plane_at(angle))
+
+
 def multi_sphere4() -> Scene:
     """models/multi_sphere.xml:30-51 (e 1.0, mu 0.0: sim_overrides.py:22-27)."""
     kind, mass, inertia, size = _spheres(4, 0.1, M_SPHERE_R01, I_SPHERE_R01)

@@ -18,6 +18,21 @@ the scene, one World call per environment.
 loop it replaces, step(EVERY) + get_state() per sample, on the same batch and
 start state (seconds per run; bytes sampled per second next to it).
 
+--per-env: next to the plain run of every E, in the same process and
+alternating rep by rep, the same sweep through the per-environment (ENVS)
+instance of the step kernel: every environment's planes and gravity set to
+the template's values and an all-zero xfrc (set_planes / set_gravity /
+set_xfrc), and once more with planes and gravity only (with forces set every
+body takes the applied-force path, which inverts the world inertia every
+step).  Adds "batch_env", "batch_env_no_xfrc", "env_over_plain" and
+"env_no_xfrc_over_plain" to the JSON line.  (The environment counts already
+own the name --envs.)
+
+--incline-sweep N: instead, N cube-incline angles (scenes.cube_incline, 0 ..
+0.7 rad) as one batch (BatchWorld.from_scenes) against N one-environment
+batches stepped one after another, the only way to run the sweep in batches
+without per-environment planes; f64 only, seconds per `--steps` steps.
+
 Prints one JSON line and writes it to --out (default
 profiles/batch/batch_bench.json).  Needs the GPU: there is no fallback.
 """
@@ -59,6 +74,72 @@ def bench_batch(rb, sc, E, steps, reps, dtype, law="mujoco"):
                 raise RuntimeError(f"{failed} environments failed")
             rates.append(E * steps / dt)
     return _summary(rates)
+
+
+def bench_batch_env(rb, sc, E, steps, reps, dtype):
+    """The plain instance and the ENVS instance on the same sweep, alternating
+    rep by rep in one process: three batches of the same start state, one
+    plain, one with per-environment planes and gravity equal to the
+    template's and a zero xfrc, one with those planes and gravity only."""
+    q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
+    v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
+    with rb.BatchWorld(sc, E, dtype=dtype) as plain, rb.BatchWorld(sc, E, dtype=dtype) as env, \
+            rb.BatchWorld(sc, E, dtype=dtype) as env_nx:
+        for b in (env, env_nx):
+            b.set_planes(sc.planes)
+            b.set_gravity(sc.gravity)
+        env.set_xfrc(np.zeros(6))
+        rates = {"plain": [], "env": [], "env_nx": []}
+        for b in (plain, env, env_nx):
+            b.set_params(restitution=np.linspace(0.5, 1.0, E))
+            b.step(steps)                               # warm-up
+        for _ in range(reps):
+            for name, b in (("plain", plain), ("env", env), ("env_nx", env_nx)):
+                b.set_state(q, v)
+                t0 = time.perf_counter()
+                failed = b.step(steps)
+                dt = time.perf_counter() - t0
+                if failed:
+                    raise RuntimeError(f"{failed} environments failed")
+                rates[name].append(E * steps / dt)
+    return _summary(rates["plain"]), _summary(rates["env"]), _summary(rates["env_nx"])
+
+
+def bench_incline_sweep(rb, n, steps, reps):
+    """n cube-incline angles: one batch of n environments against n batches of
+    one environment stepped one after another, alternating; seconds per run."""
+    from rbhip import scenes
+    scs = [scenes.cube_incline(0.7 * k / max(n - 1, 1)) for k in range(n)]
+    q = np.stack([sc.qpos0 for sc in scs])
+    v = np.stack([sc.qvel0 for sc in scs])
+    ones = [rb.BatchWorld(sc, 1) for sc in scs]
+    try:
+        with rb.BatchWorld.from_scenes(scs) as sweep:
+            sweep.step(steps)                           # warm-up of both
+            for b in ones:
+                b.step(steps)
+            t_sweep, t_ones = [], []
+            for _ in range(reps):
+                sweep.set_state(q, v)
+                t0 = time.perf_counter()
+                sweep.step(steps)
+                t_sweep.append(time.perf_counter() - t0)
+                for k, b in enumerate(ones):
+                    b.set_state(q[k:k + 1], v[k:k + 1])
+                t0 = time.perf_counter()
+                for b in ones:
+                    b.step(steps)
+                t_ones.append(time.perf_counter() - t0)
+            sq, sv = sweep.get_state()
+            same = all(np.array_equal(np.concatenate(b.get_state(), axis=2).view(np.uint64),
+                                      np.concatenate([sq[k:k + 1], sv[k:k + 1]], axis=2).view(np.uint64))
+                       for k, b in enumerate(ones))
+    finally:
+        for b in ones:
+            b.close()
+    out = dict(angles=n, identical=bool(same), one_batch_s=_summary(t_sweep), n_batches_s=_summary(t_ones))
+    out["speedup_median"] = out["n_batches_s"]["median"] / out["one_batch_s"]["median"]
+    return out
 
 
 def bench_sampled(rb, sc, E, steps, every, reps, dtype, law="mujoco"):
@@ -135,6 +216,10 @@ def main():
                     help="balls: scene ball_collision under the two-ball law")
     ap.add_argument("--sampled", type=int, default=0, metavar="EVERY",
                     help="time run_sampled(steps, EVERY) against step(EVERY) + get_state() in a loop")
+    ap.add_argument("--per-env", action="store_true",
+                    help="also run every E through the per-environment (ENVS) instance, alternating with the plain run")
+    ap.add_argument("--incline-sweep", type=int, default=0, metavar="N",
+                    help="N cube-incline angles as one batch against N one-environment batches")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "batch_bench.json"))
     a = ap.parse_args()
 
@@ -147,13 +232,26 @@ def main():
                version=rbhip.load().rb_version().decode())
     if a.law != "mujoco":
         res["law"] = a.law
-    if a.sampled:
+    if a.incline_sweep:
+        res.update(scene="cube_incline", bodies_per_env=1, dtype="f64", unit="seconds per run")
+        res["incline_sweep"] = bench_incline_sweep(rbhip, a.incline_sweep, a.steps, a.reps)
+    elif a.sampled:
         res["unit"] = "seconds per run"
         res["every"] = a.sampled
         res["sampled"] = {str(E): bench_sampled(rbhip, sc, E, a.steps, a.sampled, a.reps, a.dtype, a.law) for E in a.envs}
     else:
         res["world"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, a.law)
-        res["batch"] = {str(E): bench_batch(rbhip, sc, E, a.steps, a.reps, a.dtype, a.law) for E in a.envs}
+        if a.per_env:
+            if a.law != "mujoco":
+                raise SystemExit("--per-env: the two-ball law takes no per-environment planes or forces")
+            both = {str(E): bench_batch_env(rbhip, sc, E, a.steps, a.reps, a.dtype) for E in a.envs}
+            res["batch"] = {E: r[0] for E, r in both.items()}
+            res["batch_env"] = {E: r[1] for E, r in both.items()}
+            res["batch_env_no_xfrc"] = {E: r[2] for E, r in both.items()}
+            res["env_over_plain"] = {E: r[1]["median"] / r[0]["median"] for E, r in both.items()}
+            res["env_no_xfrc_over_plain"] = {E: r[2]["median"] / r[0]["median"] for E, r in both.items()}
+        else:
+            res["batch"] = {str(E): bench_batch(rbhip, sc, E, a.steps, a.reps, a.dtype, a.law) for E in a.envs}
         res["world_after"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, a.law)
         w = res["world"]["median"]
         res["ratio_vs_world"] = {E: dict(median=r["median"] / w, min=r["min"] / w, max=r["max"] / w)
