@@ -27,7 +27,7 @@
 #include "rb_device.hpp"
 #include "rb_grid.hpp"
 #include "rb_internal.hpp"
-#include "rb_balls.hpp"   // pair_impulse, ball_iinv, ball_ground, ball_hit (shared with rb_batch.hip)
+#include "rb_balls.hpp"   // the law itself, shared with rb_batch.hip: this unit is how a world runs it
 
 namespace rb {
 
@@ -50,29 +50,15 @@ __device__ __forceinline__ void ball_body(const StepParams<T> &p, int32_t l, int
     });
 
     // each pair from the post-ground state of both balls, deltas accumulated
-    // in ascending partner id (ball_collision.py:100-118)
+    // in ascending partner id (ball_pair: ball_collision.py:100-118)
     V3<T> x = xo, v = vo, w = wo;
     int32_t nrec = 0;
     for (int s = 0; s < np_; ++s) {
         const int32_t j = s_id[s * STEP_BLOCK + tid];
         const Snap<T> sj = p.snap_cur[j];
         const Vel<T> vj = p.vel_cur[j];
-        const V3<T> xj = {sj.x, sj.y, sj.z};
-        const T mj = p.cs.mass()[j];
-        const bool self_a = i < j;
-        const V3<T> pa = self_a ? xo : xj, pb = self_a ? xj : xo;
-        const V3<T> va = self_a ? vo : V3<T>{vj.vx, vj.vy, vj.vz};
-        const V3<T> wa = self_a ? wo : V3<T>{vj.wx, vj.wy, vj.wz};
-        const T ma = self_a ? mi : mj, ra = self_a ? ri : sj.r, rb = self_a ? sj.r : ri;
-        const M3<T> Ia = self_a ? Ii : ball_iinv(mj, sj.r);
-        const V3<T> diff = {pb.x - pa.x, pb.y - pa.y, pb.z - pa.z};         // :100
-        const T dist = sqroot(np_dot(diff, diff));                          // :101
-        const T dd = dist + T(1e-8);
-        const V3<T> n = {diff.x / dd, diff.y / dd, diff.z / dd};            // :104
-        const V3<T> cp = {(pa.x + pb.x) / T(2), (pa.y + pb.y) / T(2), (pa.z + pb.z) / T(2)};   // :105
-        const V3<T> r1 = {cp.x - pa.x, cp.y - pa.y, cp.z - pa.z};           // :106
-        const V3<T> imp = pair_impulse(ma, Ia, va, wa, r1, n, p.e, p.mu);   // :109-110
-        const T corr = (((ra + rb) + p.tol) - dist) / T(2);                 // :116
+        const T dist = ball_pair(xo, vo, wo, mi, ri, Ii, V3<T>{sj.x, sj.y, sj.z}, V3<T>{vj.vx, vj.vy, vj.vz},
+                                 V3<T>{vj.wx, vj.wy, vj.wz}, p.cs.mass()[j], sj.r, i < j, p.e, p.mu, p.tol, x, v, w);
         if (p.rec_count) {
             if (nrec < p.maxrec) {
                 const int64_t o = (int64_t)l * p.maxrec + nrec;
@@ -81,18 +67,6 @@ __device__ __forceinline__ void ball_body(const StepParams<T> &p, int32_t l, int
                 p.rec_dist[o] = dist;
             }
             ++nrec;
-        }
-        if (self_a) {
-            const V3<T> dw = np_matvec(Ii, np_cross(r1, imp));
-            v = {v.x + imp.x / mi, v.y + imp.y / mi, v.z + imp.z / mi};     // :111
-            w = {w.x + dw.x, w.y + dw.y, w.z + dw.z};                       // :112
-            x = {x.x - corr * n.x, x.y - corr * n.y, x.z - corr * n.z};     // :117
-        } else {
-            const V3<T> r2 = {cp.x - pb.x, cp.y - pb.y, cp.z - pb.z};       // :107
-            const V3<T> dw = np_matvec(Ii, np_cross(r2, imp));
-            v = {v.x - imp.x / mi, v.y - imp.y / mi, v.z - imp.z / mi};     // :113
-            w = {w.x - dw.x, w.y - dw.y, w.z - dw.z};                       // :114
-            x = {x.x + corr * n.x, x.y + corr * n.y, x.z + corr * n.z};     // :118
         }
     }
     if (p.rec_count) p.rec_count[l] = nrec;

@@ -1,8 +1,8 @@
-// rb_balls.hpp — the device functions of the two-ball law
-// (src/simulation/ball_collision.py) that the world's kernels (rb_balls.hip)
-// and the batch kernel (rb_batch.hip) share: an environment of a batch steps
-// with the very expressions a world steps with, so the two agree bit for bit
-// (as rb_device.hpp / rb_body.hpp for the default law).
+// rb_balls.hpp — the two-ball law (src/simulation/ball_collision.py), each
+// part written once: impulse, ground phase, reach test, and the evaluation of
+// a pair (ball_pair).  The world's kernels (rb_balls.hip) and the batch kernel
+// (rb_batch.hip) differ only in where a ball's partners come from, so a batch
+// and a world agree bit for bit (as rb_device.hpp / rb_body.hpp for the default law).
 #pragma once
 #include "rb_device.hpp"
 #include "rb_internal.hpp"
@@ -70,6 +70,42 @@ template <typename T> __device__ __forceinline__ bool ball_hit(V3<T> pa, T ra, V
         if (d2 < L2 * (T(1) - sq_margin<T>())) return true;
     }
     return sqroot(d2) < L;
+}
+
+// One pair within reach, from the post-ground state of both balls, as the
+// calling ball sees it (ball_collision.py:100-118).  The ball of the lower id
+// is a (self_a: the caller is); the impulse is the one from a's side, applied
+// + to a and - to b, and the positions are pushed apart by half the overlap.
+// Adds the caller's share to its running x, v, w; returns |p_b - p_a|.
+template <typename T>
+__device__ __forceinline__ T ball_pair(V3<T> xo, V3<T> vo, V3<T> wo, T mi, T ri, const M3<T> &Ii, V3<T> xj, V3<T> vj,
+                                       V3<T> wj, T mj, T rj, bool self_a, T e, T mu, T tol, V3<T> &x, V3<T> &v,
+                                       V3<T> &w) {
+    const V3<T> pa = self_a ? xo : xj, pb = self_a ? xj : xo;
+    const V3<T> va = self_a ? vo : vj, wa = self_a ? wo : wj;
+    const T ma = self_a ? mi : mj, ra = self_a ? ri : rj, rb = self_a ? rj : ri;
+    const M3<T> Ia = self_a ? Ii : ball_iinv(mj, rj);
+    const V3<T> diff = {pb.x - pa.x, pb.y - pa.y, pb.z - pa.z};             // :100
+    const T dist = sqroot(np_dot(diff, diff));                              // :101
+    const T dd = dist + T(1e-8);
+    const V3<T> n = {diff.x / dd, diff.y / dd, diff.z / dd};                // :104
+    const V3<T> cp = {(pa.x + pb.x) / T(2), (pa.y + pb.y) / T(2), (pa.z + pb.z) / T(2)};   // :105
+    const V3<T> r1 = {cp.x - pa.x, cp.y - pa.y, cp.z - pa.z};               // :106
+    const V3<T> imp = pair_impulse(ma, Ia, va, wa, r1, n, e, mu);           // :109-110
+    const T corr = (((ra + rb) + tol) - dist) / T(2);                       // :116
+    if (self_a) {
+        const V3<T> dw = np_matvec(Ii, np_cross(r1, imp));
+        v = {v.x + imp.x / mi, v.y + imp.y / mi, v.z + imp.z / mi};         // :111
+        w = {w.x + dw.x, w.y + dw.y, w.z + dw.z};                           // :112
+        x = {x.x - corr * n.x, x.y - corr * n.y, x.z - corr * n.z};         // :117
+    } else {
+        const V3<T> r2 = {cp.x - pb.x, cp.y - pb.y, cp.z - pb.z};           // :107
+        const V3<T> dw = np_matvec(Ii, np_cross(r2, imp));
+        v = {v.x - imp.x / mi, v.y - imp.y / mi, v.z - imp.z / mi};         // :113
+        w = {w.x - dw.x, w.y - dw.y, w.z - dw.z};                           // :114
+        x = {x.x + corr * n.x, x.y + corr * n.y, x.z + corr * n.z};         // :118
+    }
+    return dist;
 }
 
 }  // namespace rb

@@ -13,13 +13,16 @@
 // stores once.  Each step is body_update's sequence (rb_step.hpp) built
 // from the same functions (rb_body.hpp, rb_device.hpp), so an environment
 // steps bit-identically to a world of the same scene.  The two-ball law
-// (batch_balls_kernel) has the same shape, built from rb_balls.hpp.
+// (batch_balls_kernel) has the same shape; the law itself, pair evaluation
+// included, is in rb_balls.hpp, as for the world's kernels.  The two step
+// kernels share a frame (step constants, sampling tick, epilogue).
 //
 // Sampled runs (rb_batch_run_sampled) launch the recording instances (REC):
 // inside the register loop, after every every-th step of the run, a lane
 // stores its committed state into a slot of the sample buffer, laid out as
 // the state rows are (rows of E * M reals per slot: a wave's stores are
 // contiguous); batch_samples_out_kernel turns slots into the boundary's rows.
+#include <type_traits>
 #include "rb_device.hpp"
 #include "rb_grid.hpp"
 #include "rb_internal.hpp"
@@ -71,6 +74,42 @@ template <typename T> __device__ __forceinline__ void env_planes_fill(const Batc
     }
 }
 
+// ---- the frame the two step kernels share ------------------------------------
+// (The lane mapping is not part of it: as a function it compiled the plain
+// batch_step_kernel instances to different code, measured 2 % slower: DESIGN 4.3.)
+
+// The step constants both laws read (ENVS: the environment's gravity, where set)
+template <typename T, bool ENVS>
+__device__ __forceinline__ void batch_consts(const BatchParams<T> &p, int64_t ev, StepParams<T> &sp) {
+    sp.g[0] = p.g[0]; sp.g[1] = p.g[1]; sp.g[2] = p.g[2];
+    sp.dt = p.dt;
+    sp.e = p.env_e ? p.env_e[ev] : p.e;
+    sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
+    if constexpr (ENVS)
+        if (p.env_g) { sp.g[0] = p.env_g[ev]; sp.g[1] = p.env_g[p.E + ev]; sp.g[2] = p.env_g[2 * p.E + ev]; }
+}
+
+// REC: steps to the next sample and its slot; a lane ticks after every step and
+// on a sampled one stores its committed state (a failed environment's: frozen)
+struct SampleTick { int32_t until, slot; };
+template <typename T>
+__device__ __forceinline__ void sample_tick(const BatchParams<T> &p, SampleTick &t, bool active, int64_t g, const V3<T> &x,
+                                            const Q4<T> &q, const V3<T> &v, const V3<T> &w) {
+    if (--t.until == 0) {
+        if (active) sample_store(p, t.slot, g, x, q, v, w);
+        ++t.slot;
+        t.until = p.every;
+    }
+}
+
+// The end of a launch, by an environment's first lane: steps completed, failure code
+template <typename T> __device__ __forceinline__ void batch_finish(const BatchParams<T> &p, int b, int64_t env, int32_t done) {
+    if (b == 0) {
+        if (done > 0) p.steps_done[env] += done;
+        if (done < p.k && p.code[env] == 0) p.code[env] = BATCH_EDOM;
+    }
+}
+
 // BOX: the template environment is one box (M == 1); else spheres only
 // REC: the recording instance of a sampled run
 // ENVS: per-environment planes, gravity or applied forces are set (each of
@@ -113,18 +152,14 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
     sp.xfrc = nullptr;
     sp.rec_count = nullptr;
     sp.S = 0;
-    sp.g[0] = p.g[0]; sp.g[1] = p.g[1]; sp.g[2] = p.g[2];
-    sp.dt = p.dt;
+    batch_consts<T, ENVS>(p, ev, sp);
     sp.thr = p.thr;
-    sp.e = p.env_e ? p.env_e[ev] : p.e;
-    sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
     sp.oriented = p.oriented;
 
-    // ---- ENVS: the environment's gravity and planes, the body's applied force
+    // ---- ENVS: the environment's planes, the body's applied force -----------
     V3<T> xf = {T(0), T(0), T(0)}, xt = xf;
     EnvPlanes<T> epl{};
     if constexpr (ENVS) {
-        if (p.env_g) { sp.g[0] = p.env_g[ev]; sp.g[1] = p.env_g[p.E + ev]; sp.g[2] = p.env_g[2 * p.E + ev]; }
         if (p.env_xfrc) {
             const int64_t N = p.E * M;
             xf = {p.env_xfrc[g], p.env_xfrc[N + g], p.env_xfrc[2 * N + g]};
@@ -141,7 +176,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
     s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
     __syncthreads();
 
-    int32_t until = p.phase, slot = p.samp_first;   // REC: steps to the next sample, its slot
+    SampleTick tick = {p.phase, p.samp_first};
 
     for (int s = 0; s < p.k; ++s) {
         const Snap<T> *cur = s_snap[s & 1];
@@ -198,14 +233,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
             x = xn; q = qn; v = vn; w = wn;
             ++done;
         }
-        // a failed environment's lanes record its frozen state
-        if constexpr (REC) {
-            if (--until == 0) {
-                if (active) sample_store(p, slot, g, x, q, v, w);
-                ++slot;
-                until = p.every;
-            }
-        }
+        if constexpr (REC) sample_tick(p, tick, active, g, x, q, v, w);
     }
 
     // ---- store once ------------------------------------------------------------
@@ -216,16 +244,13 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_step_kernel(BatchParams<T> 
         p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
         p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
     }
-    if (b == 0) {
-        if (done > 0) p.steps_done[env] += done;
-        if (done < p.k && p.code[env] == 0) p.code[env] = BATCH_EDOM;
-    }
+    batch_finish(p, b, env, done);
 }
 
 
-// The two-ball law (rb_balls.hpp; ball_collision.py:73-125) with the lane and
-// environment mapping of batch_step_kernel.  The registers hold a ball's true
-// state (x, v, w) and the post-ground state of the coming step (gx, gv, gw:
+// The two-ball law (ball_collision.py:73-125; every expression of it is in
+// rb_balls.hpp) with the lane and environment mapping and the frame of
+// batch_step_kernel.  The registers hold a ball's true state (x, v, w) and the post-ground state of the coming step (gx, gv, gw:
 // gravity and the ground contact depend on the ball alone), which is what the
 // partners read from LDS: positions and radius in Snap, velocity and spin in
 // Vel, both ping-pong, so a step has one barrier.  A step evaluates every
@@ -269,15 +294,10 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
     bool failed = !active || p.code[ev] != 0;
     int32_t done = 0;
 
-    // the constants ball_ground reads
+    // the constants ball_ground and ball_pair read
     StepParams<T> sp;
-    sp.g[0] = p.g[0]; sp.g[1] = p.g[1]; sp.g[2] = p.g[2];
-    sp.dt = p.dt;
-    sp.e = p.env_e ? p.env_e[ev] : p.e;
-    sp.mu = p.env_mu ? p.env_mu[ev] : p.mu;
     sp.ground = p.ground;
-    if constexpr (ENVS)
-        if (p.env_g) { sp.g[0] = p.env_g[ev]; sp.g[1] = p.env_g[p.E + ev]; sp.g[2] = p.env_g[2 * p.E + ev]; }
+    batch_consts<T, ENVS>(p, ev, sp);
     const T tol = p.tol;
 
     // the first step's ground phase, from the true state
@@ -289,7 +309,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
     s_vel[0][lane] = Vel<T>{gv.x, gv.y, gv.z, gw.x, gw.y, gw.z, T(0), T(0)};
     __syncthreads();
 
-    int32_t until = p.phase, slot = p.samp_first;   // REC: steps to the next sample, its slot
+    SampleTick tick = {p.phase, p.samp_first};
 
     for (int s = 0; s < p.k; ++s) {
         const Snap<T> *cur = s_snap[s & 1];
@@ -299,7 +319,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
         bool bad = !cell_of(gx.x, gx.y, gx.z, p.inv_cs, cx, cy, cz);
 
         // ---- every other ball of the environment, ascending id ---------------
-        // (ball_collision.py:100-118; the expressions of ball_body)
+        // (ball_pair, rb_balls.hpp; the partner's Vel and mass are read on a hit only)
         const V3<T> xo = gx, vo = gv, wo = gw;
         V3<T> xa = xo, va = vo, wa = wo;
         for (int j = 0; j < M; ++j) {
@@ -309,32 +329,8 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
             const bool self_a = b < j;
             if (!(self_a ? ball_hit(xo, ri, xj, sj.r, tol) : ball_hit(xj, sj.r, xo, ri, tol))) continue;
             const Vel<T> vj = curv[ebase + j];
-            const T mj = s_mass[ebase + j];
-            const V3<T> pa = self_a ? xo : xj, pb = self_a ? xj : xo;
-            const V3<T> vA = self_a ? vo : V3<T>{vj.vx, vj.vy, vj.vz};
-            const V3<T> wA = self_a ? wo : V3<T>{vj.wx, vj.wy, vj.wz};
-            const T ma = self_a ? mi : mj, ra = self_a ? ri : sj.r, rb = self_a ? sj.r : ri;
-            const M3<T> Ia = self_a ? Ii : ball_iinv(mj, sj.r);
-            const V3<T> diff = {pb.x - pa.x, pb.y - pa.y, pb.z - pa.z};         // :100
-            const T dist = sqroot(np_dot(diff, diff));                          // :101
-            const T dd = dist + T(1e-8);
-            const V3<T> n = {diff.x / dd, diff.y / dd, diff.z / dd};            // :104
-            const V3<T> cp = {(pa.x + pb.x) / T(2), (pa.y + pb.y) / T(2), (pa.z + pb.z) / T(2)};   // :105
-            const V3<T> r1 = {cp.x - pa.x, cp.y - pa.y, cp.z - pa.z};           // :106
-            const V3<T> imp = pair_impulse(ma, Ia, vA, wA, r1, n, sp.e, sp.mu); // :109-110
-            const T corr = (((ra + rb) + tol) - dist) / T(2);                   // :116
-            if (self_a) {
-                const V3<T> dw = np_matvec(Ii, np_cross(r1, imp));
-                va = {va.x + imp.x / mi, va.y + imp.y / mi, va.z + imp.z / mi};     // :111
-                wa = {wa.x + dw.x, wa.y + dw.y, wa.z + dw.z};                       // :112
-                xa = {xa.x - corr * n.x, xa.y - corr * n.y, xa.z - corr * n.z};     // :117
-            } else {
-                const V3<T> r2 = {cp.x - pb.x, cp.y - pb.y, cp.z - pb.z};           // :107
-                const V3<T> dw = np_matvec(Ii, np_cross(r2, imp));
-                va = {va.x - imp.x / mi, va.y - imp.y / mi, va.z - imp.z / mi};     // :113
-                wa = {wa.x - dw.x, wa.y - dw.y, wa.z - dw.z};                       // :114
-                xa = {xa.x + corr * n.x, xa.y + corr * n.y, xa.z + corr * n.z};     // :118
-            }
+            ball_pair(xo, vo, wo, mi, ri, Ii, xj, V3<T>{vj.vx, vj.vy, vj.vz}, V3<T>{vj.wx, vj.wy, vj.wz},
+                      s_mass[ebase + j], sj.r, self_a, sp.e, sp.mu, tol, xa, va, wa);
         }
 
         // ---- integrate (:121-122): the true end-of-step state ------------------
@@ -356,13 +352,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
             gx = ngx; gv = ngv; gw = ngw;
             ++done;
         }
-        if constexpr (REC) {
-            if (--until == 0) {
-                if (active) sample_store(p, slot, g, x, q, v, w);
-                ++slot;
-                until = p.every;
-            }
-        }
+        if constexpr (REC) sample_tick(p, tick, active, g, x, q, v, w);
     }
 
     // ---- store once ------------------------------------------------------------
@@ -372,10 +362,7 @@ __global__ __launch_bounds__(BATCH_BLOCK) void batch_balls_kernel(BatchParams<T>
         p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
         p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
     }
-    if (b == 0) {
-        if (done > 0) p.steps_done[env] += done;
-        if (done < p.k && p.code[env] == 0) p.code[env] = BATCH_EDOM;
-    }
+    batch_finish(p, b, env, done);
 }
 
 // Slots [first, first + n) of the sample buffer into the boundary's rows (the
@@ -452,6 +439,12 @@ template <typename T> __global__ __launch_bounds__(256) void batch_bound_kernel(
 
 static unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// a runtime flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{})
+template <typename F> static void as_constant(bool flag, F &&f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, bool balls, bool rec, hipStream_t s) {
     if (p.E <= 0 || p.k <= 0) return hipSuccess;
     if (balls && box) return hipErrorInvalidValue;
@@ -464,29 +457,21 @@ template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool
     // the ENVS instances: only with a per-environment array set
     if (balls) {
         if (p.env_planes || p.env_xfrc) return hipErrorInvalidValue;    // (refused by the setters under this law)
-        if (p.env_g) {
-            if (rec) hipLaunchKernelGGL((batch_balls_kernel<T, true, true>), gr, bl, 0, s, p);
-            else hipLaunchKernelGGL((batch_balls_kernel<T, false, true>), gr, bl, 0, s, p);
-        } else {
-            if (rec) hipLaunchKernelGGL((batch_balls_kernel<T, true, false>), gr, bl, 0, s, p);
-            else hipLaunchKernelGGL((batch_balls_kernel<T, false, false>), gr, bl, 0, s, p);
-        }
-    } else if (p.env_planes || p.env_g || p.env_xfrc) {
-        // the wave's planes in LDS: [n_planes][6][environments per wave]
-        const size_t lds = (size_t)epw * (size_t)p.n_planes * 6 * sizeof(T);
-        if (rec) {
-            if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, true, true>), gr, bl, lds, s, p);
-            else hipLaunchKernelGGL((batch_step_kernel<T, false, true, true>), gr, bl, lds, s, p);
-        } else {
-            if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, false, true>), gr, bl, lds, s, p);
-            else hipLaunchKernelGGL((batch_step_kernel<T, false, false, true>), gr, bl, lds, s, p);
-        }
-    } else if (rec) {
-        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, true, false>), gr, bl, 0, s, p);
-        else hipLaunchKernelGGL((batch_step_kernel<T, false, true, false>), gr, bl, 0, s, p);
+        as_constant(rec, [&](auto REC) {
+            as_constant(p.env_g != nullptr, [&](auto ENVS) {
+                hipLaunchKernelGGL((batch_balls_kernel<T, REC.value, ENVS.value>), gr, bl, 0, s, p);
+            });
+        });
     } else {
-        if (box) hipLaunchKernelGGL((batch_step_kernel<T, true, false, false>), gr, bl, 0, s, p);
-        else hipLaunchKernelGGL((batch_step_kernel<T, false, false, false>), gr, bl, 0, s, p);
+        as_constant(box, [&](auto BOX) {
+            as_constant(rec, [&](auto REC) {
+                as_constant(p.env_planes || p.env_g || p.env_xfrc, [&](auto ENVS) {
+                    // ENVS: the wave's planes in LDS, [n_planes][6][environments per wave]
+                    const size_t lds = ENVS.value ? (size_t)epw * (size_t)p.n_planes * 6 * sizeof(T) : 0;
+                    hipLaunchKernelGGL((batch_step_kernel<T, BOX.value, REC.value, ENVS.value>), gr, bl, lds, s, p);
+                });
+            });
+        });
     }
     return hipGetLastError();
 }

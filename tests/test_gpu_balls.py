@@ -69,6 +69,35 @@ def test_ball_pile_vs_oracle(rb, oracle, dtype):
     assert np.array_equal(c[0], cnt) and np.array_equal(c[1], par)
 
 
+def test_recorded_pair_dist_is_the_centre_distance(rb):
+    """The world's contact record of a pair holds the |p_b - p_a| the shared
+    pair evaluation (ball_pair, rb_balls.hpp) returns.  Two equal balls meet in
+    the air, far above the ground, so the post-ground positions the pair is
+    evaluated on are the positions read before the step.  Bound: fused or
+    separate rounding of the three products moves the root by a few 1e-16
+    relative; the neighbouring dist + 1e-8 is 1e-7 relative away."""
+    sc = rb.scenes.ball_collision(spin=True)
+    qpos = sc.qpos0.copy()
+    qpos[:, :3] = [[-0.3, 0.0, 1.0], [0.3, 0.06, 1.05]]          # closing at 2 m/s: in reach within 20 steps
+    with rb.World(sc.with_(qpos0=qpos), law="balls", tol=0.01) as w:
+        w.record_contacts(True)
+        for _ in range(40):
+            before = w.get_state()[0].reshape(-1, 7)[:, :3].copy()
+            w.step(1)
+            cnt, par, kind, dist = w.contacts()
+            if cnt.any():
+                break
+        else:
+            pytest.fail("the balls never met")
+    assert before[:, 2].min() > 0.5                              # radius 0.1: no ground contact
+    assert cnt.tolist() == [1, 1] and par.tolist() == [1, 0] and kind.tolist() == [16, 16]
+    d = before[1] - before[0]
+    want = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    assert 0.15 < want < 0.21
+    print("recorded", dist.tolist(), "expected", want, "relative", (np.abs(dist - want) / want).tolist())
+    assert np.all(np.abs(dist - want) <= 1e-14 * want)
+
+
 def test_law_switch_round_trip(rb, oracle):
     """mujoco -> balls -> mujoco on one world continues each law's run."""
     sc = rb.scenes.balls_pile(8, 8, seed=3)
