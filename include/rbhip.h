@@ -347,8 +347,7 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * under either contact law (rb_batch_set_contact_law).
  * Arrays are environment-major: body k of environment e at row e*M + k.
  * Not covered (use rb_world): contact recording, caller streams and
- * asynchronous stepping, sharding, box-involved pairs (a box is accepted
- * only as the single body of its environment), per-environment plane
+ * asynchronous stepping, sharding, per-environment kinds or plane
  * counts, more than 64 bodies per environment; under RB_LAW_BALLS also
  * per-environment planes and applied forces.
  * A batch handle is not thread-safe; every call is synchronous.
@@ -363,8 +362,19 @@ typedef struct rb_batch rb_batch;
  * environment (n_bodies = M in 1..64, world_size 1, rank 0; max_partners and
  * bucket_capacity unused: every body may touch all others), replicated
  * n_envs times.  RB_EUNSUPPORTED for a template with a box body and more
- * than one body. */
+ * than one body (rb_batch_create_mixed takes it). */
 int  rb_batch_create(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs);
+/* rb_batch_create that also accepts any mix of spheres and boxes in a
+ * template of 2..64 bodies (a column or pile of cubes: the reference's
+ * stated goal is stacking): box-involved pairs are evaluated inside the
+ * batch, every environment bit-identically to an rb_world of its scene with
+ * max_partners 32.  Additive to 0.4 (rb_version is unchanged).  A sphere-only
+ * or one-box template gives exactly the batch rb_batch_create gives.  Every
+ * other rb_batch_* call works on such a batch as on any other (sizes set by
+ * rb_batch_set_bodies are per environment, the kinds stay the template's);
+ * rb_batch_set_contact_law(RB_LAW_BALLS) is RB_EUNSUPPORTED: that law takes
+ * spheres only. */
+int  rb_batch_create_mixed(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs);
 void rb_batch_destroy(rb_batch *b);
 /* Per-environment restitution / friction, [n_envs] each; NULL = use the
  * scalar given to rb_batch_step.  Replaces the per-scene constants of

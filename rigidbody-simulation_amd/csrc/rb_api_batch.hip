@@ -17,6 +17,8 @@ struct rb_batch {
     int64_t E = 0, N = 0;              // environments, body slots (E * M)
     int32_t M = 0, n_planes = 0, oriented = 1;
     bool box = false;                  // the template is one box
+    bool mixed = false;                // a box among several bodies (rb_batch_create_mixed): batch_mixed_kernel
+    int32_t *d_kind = nullptr;         // [M] the template's kinds on the device (mixed)
     std::vector<int32_t> kind;         // [M] the template's kinds
     double planes[RB_MAX_PLANES][6] = {};
     double g[3] = {};
@@ -54,7 +56,7 @@ void free_batch(rb_batch *b) {
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc};
+                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -141,7 +143,7 @@ template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double
     BatchParams<T> p{};
     p.snap = dp<Snap<T>>(b->snap, 0);
     p.st = BodyState<T>{dp<T>(b->state, 0), b->N};
-    p.cs = BodyConsts<T>{dp<T>(b->consts, 0), b->N, nullptr};
+    p.cs = BodyConsts<T>{dp<T>(b->consts, 0), b->N, b->d_kind};
     p.env_e = b->have_e ? dp<T>(b->env_e, 0) : nullptr;
     p.env_mu = b->have_mu ? dp<T>(b->env_mu, 0) : nullptr;
     p.code = b->code;
@@ -162,6 +164,12 @@ template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double
     p.env_g = b->have_g ? dp<T>(b->env_g, 0) : nullptr;
     p.env_xfrc = b->have_xfrc ? dp<T>(b->env_xfrc, 0) : nullptr;
     return p;
+}
+
+// one launch of the batch's step kernel (rec: the recording instance)
+template <typename T> hipError_t batch_launch(rb_batch *b, const BatchParams<T> &p, bool rec) {
+    if (b->mixed) return launch_batch_mixed<T>(p, rec, b->stream);
+    return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, rec, b->stream);
 }
 
 int batch_check_step(const rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr) {
@@ -230,12 +238,8 @@ int batch_check_ids(const rb_batch *b, const int64_t *env_ids, int64_t n) {
     return RB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
-    ApiScope api_scope_(d ? d->device : -1);
+// rb_batch_create / rb_batch_create_mixed (mixed: a box among several bodies is accepted)
+int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mixed) {
     if (!out || !d) return fail(RB_EINVAL, "null argument");
     *out = nullptr;
     if (n_envs < 1) return fail(RB_EINVAL, "n_envs must be >= 1");
@@ -254,9 +258,9 @@ int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
         if (!(d->mass[k] > 0)) return fail(RB_EINVAL, "body %lld: mass must be > 0", (long long)k);
         any_box = any_box || d->kind[k] == RB_BODY_BOX;
     }
-    if (any_box && d->n_bodies > 1)
+    if (any_box && d->n_bodies > 1 && !mixed)
         return fail(RB_EUNSUPPORTED, "rb_batch: unsupported template: a box body in an environment of more than one body "
-                                     "(box-involved pairs are stepped by rb_world)");
+                                     "(box-involved pairs are stepped by rb_batch_create_mixed, or by rb_world)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RB_ENODEV, "no HIP device available");
     if (d->device < 0 || d->device >= ndev) return fail(RB_ENODEV, "device %d out of range (have %d)", d->device, ndev);
@@ -268,7 +272,8 @@ int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
     b->E = n_envs;
     b->M = (int32_t)d->n_bodies;
     b->N = b->E * b->M;
-    b->box = any_box;
+    b->mixed = any_box && d->n_bodies > 1;
+    b->box = any_box && !b->mixed;
     b->kind.assign(d->kind, d->kind + d->n_bodies);
     b->n_planes = d->n_planes;
     for (int k = 0; k < d->n_planes; ++k)
@@ -290,6 +295,11 @@ int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
         if (hipMalloc(a.first, a.second) != hipSuccess) return bail(fail(RB_ENOMEM, "hipMalloc(%zu) failed", a.second));
         if (hipMemsetAsync(*a.first, 0, a.second, b->stream) != hipSuccess) return bail(fail(RB_ENODEV, "hipMemsetAsync failed"));
     }
+    if (b->mixed) {
+        const size_t kb = sizeof(int32_t) * (size_t)b->M;
+        if (hipMalloc((void **)&b->d_kind, kb) != hipSuccess) return bail(fail(RB_ENOMEM, "hipMalloc(%zu) failed", kb));
+        if (int rc = bput(b, b->d_kind, b->kind.data(), kb)) return bail(rc);
+    }
     // the template's constants, replicated per environment
     std::vector<double> mass(N), inertia(3 * N), size(3 * N);
     for (size_t g = 0; g < N; ++g) {
@@ -300,6 +310,20 @@ int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
     if (int rc = rb_batch_set_bodies(b, mass.data(), inertia.data(), size.data())) return bail(rc);
     *out = b;
     return RB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
+    ApiScope api_scope_(d ? d->device : -1);
+    return batch_create(out, d, n_envs, false);
+}
+
+int rb_batch_create_mixed(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
+    ApiScope api_scope_(d ? d->device : -1);
+    return batch_create(out, d, n_envs, true);
 }
 
 void rb_batch_destroy(rb_batch *b) {
@@ -404,7 +428,7 @@ int rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol) {
     if (law != RB_LAW_MUJOCO && law != RB_LAW_BALLS) return fail(RB_EINVAL, "unknown contact law %d", law);
     if (!(tol >= 0) || !(tol < 1e6)) return fail(RB_EINVAL, "tol must be finite and >= 0");
     if (law == RB_LAW_BALLS) {
-        if (b->box) return fail(RB_EUNSUPPORTED, "the two-ball law takes spheres only");
+        if (b->box || b->mixed) return fail(RB_EUNSUPPORTED, "the two-ball law takes spheres only");
         const double ground[6] = {0, 0, 1, 0, 0, 0};
         if (b->n_planes > 1 || (b->n_planes == 1 && memcmp(b->planes[0], ground, sizeof(ground)) != 0))
             return fail(RB_EUNSUPPORTED, "the two-ball law's only plane is the z = 0 ground (ball_collision.py:88-90)");
@@ -473,7 +497,7 @@ int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, d
         const int32_t k = (int32_t)std::min<int64_t>(left, BATCH_CHUNK);
         HIPCHK(by_real(b->dtype, [&](auto t) {
             using T = decltype(t);
-            return launch_batch_step<T>(batch_params<T>(b, k, dt, e, mu, thr), b->box, b->law == RB_LAW_BALLS, false, b->stream);
+            return batch_launch<T>(b, batch_params<T>(b, k, dt, e, mu, thr), false);
         }));
     }
     return batch_report(b, n_failed);
@@ -519,14 +543,14 @@ int rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, 
             using T = decltype(t);
             BatchParams<T> p = batch_params<T>(b, (int32_t)l.steps, dt, e, mu, thr);
             if (l.samples == 0)          // nothing to record in this launch: the plain instance
-                return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, false, b->stream);
+                return batch_launch<T>(b, p, false);
             p.samp = reinterpret_cast<T *>(slots);
             p.every = (int32_t)std::min<int64_t>(every, BATCH_CHUNK + 1);   // (a second sample lies past the launch)
             p.phase = (int32_t)l.phase;                                     // (<= steps <= RB_BATCH_CHUNK here)
             p.samp_first = (int32_t)l.first;
             p.samp_slots = (int32_t)fit;
             p.samp_rows = rows;
-            return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, true, b->stream);
+            return batch_launch<T>(b, p, true);
         }));
         if (l.drain == 0) continue;
         // a plain synchronous drain: transpose, download, wait

@@ -468,7 +468,8 @@ constexpr int32_t BATCH_EDOM = -33;      // RB_EDOM, as the status word records 
 template <typename T> struct BatchParams {
     Snap<T> *snap;                       // [E * M] x y z, bounding radius
     BodyState<T> st;                     // rows of E * M
-    BodyConsts<T> cs;                    // rows of E * M (kind unused: the template's kinds are uniform)
+    BodyConsts<T> cs;                    // rows of E * M (kind: the template's M kinds, uniform across environments:
+                                         // read by batch_mixed_kernel only, else nullptr)
     const T *env_e, *env_mu;             // [E] restitution / friction, or nullptr: the scalars below
     int32_t *code;                       // [E] 0 | BATCH_EDOM
     int64_t *steps_done;                 // [E] steps completed since the environment's last set_state
@@ -520,6 +521,9 @@ template <typename T> struct EnvPlanes {
 // With one of p.env_planes / env_g / env_xfrc set it is the ENVS instance,
 // whose dynamic LDS (floor(64 / M) * n_planes * 6 reals) holds the planes.
 template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool box, bool balls, bool rec, hipStream_t s);
+// the same for a template that mixes spheres and boxes (rb_batch_boxes.hip:
+// batch_mixed_kernel); p.cs.kind: the template's M kinds
+template <typename T> hipError_t launch_batch_mixed(const BatchParams<T> &p, bool rec, hipStream_t s);
 // slots [first, first + n) of the sample buffer -> the boundary's rows, in
 // double: qpos [n][E * M][7] and (rows == 13) qvel [n][E * M][6]
 template <typename T>

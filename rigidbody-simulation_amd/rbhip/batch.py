@@ -9,7 +9,9 @@ and (set_planes / set_gravity / set_xfrc, or one Scene per environment
 through from_scenes) its own planes, gravity and applied forces: the incline
 angle of cube_incline.py, model.opt.gravity, data.xfrc_applied.  Every
 environment steps bit-identically to a World of the same scene, under the
-default contact law or the two-ball law of ball_collision.py.
+default contact law or the two-ball law of ball_collision.py.  A scene may
+mix spheres and boxes (scenes.box_pile: stacks of cubes), box-involved pairs
+included; from_scenes over a list of seeds is an ensemble of piles.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
 multi_sphere_logger.py), one per environment, sampled on the device.
@@ -28,8 +30,9 @@ from .scenes import Scene
 class BatchWorld:
     def __init__(self, scene: Scene, n_envs: int, device: int = 0, dtype: str = "f64",
                  normal_convention: Optional[str] = None, law: str = "mujoco", tol: float = 0.01):
-        """scene: the template environment (1..64 bodies; a box only alone),
-        replicated n_envs times with the scene's initial state.
+        """scene: the template environment (1..64 bodies, spheres and boxes
+        in any mix: scenes.box_pile), replicated n_envs times with the
+        scene's initial state.
 
         law: "mujoco" (the per-body law of collision.py /
         multi_sphere_bounce.py) or "balls" (the symmetric two-ball law of
@@ -58,7 +61,10 @@ class BatchWorld:
             d.gravity[k] = float(scene.gravity[k])
         h = C.c_void_p()
         self._h = None
-        _lib.check(L.rb_batch_create(C.byref(h), C.byref(d), self.n_envs), "rb_batch_create")
+        # a box among several bodies: the entry point that steps box-involved pairs
+        mixed = scene.n > 1 and bool(np.any(kind != 0))
+        create = "rb_batch_create_mixed" if mixed else "rb_batch_create"
+        _lib.check(getattr(L, create)(C.byref(h), C.byref(d), self.n_envs), create)
         self._h = h
         self._L = L
         E, M = self.n_envs, self.n_bodies

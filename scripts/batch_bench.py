@@ -33,6 +33,11 @@ own the name --envs.)
 batches stepped one after another, the only way to run the sweep in batches
 without per-environment planes; f64 only, seconds per `--steps` steps.
 
+--box-pile NX,NY,LAYERS: the same measurement on scenes.box_pile(NX, NY,
+LAYERS) (columns of cubes, some capped with a sphere: box-involved pairs, the
+mixed-template kernel) with a friction sweep (0.2 .. 0.8 over the
+environments) against one World(scene, max_partners=32).
+
 Prints one JSON line and writes it to --out (default
 profiles/batch/batch_bench.json).  Needs the GPU: there is no fallback.
 """
@@ -58,11 +63,13 @@ def _batch(rb, sc, E, dtype, law):
     return rb.BatchWorld(sc, E, dtype=dtype) if law == "mujoco" else rb.BatchWorld(sc, E, dtype=dtype, law=law)
 
 
-def bench_batch(rb, sc, E, steps, reps, dtype, law="mujoco"):
+def bench_batch(rb, sc, E, steps, reps, dtype, law="mujoco", sweep=None):
+    """sweep: the per-environment knob, {name: (lo, hi)} (default: restitution 0.5 .. 1.0)"""
+    sweep = sweep or {"restitution": (0.5, 1.0)}
     q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
     v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
     with _batch(rb, sc, E, dtype, law) as b:
-        b.set_params(restitution=np.linspace(0.5, 1.0, E))
+        b.set_params(**{k: np.linspace(lo, hi, E) for k, (lo, hi) in sweep.items()})
         b.step(steps)                                   # warm-up
         rates = []
         for _ in range(reps):
@@ -194,8 +201,8 @@ def bench_sampled(rb, sc, E, steps, every, reps, dtype, law="mujoco"):
     return out
 
 
-def bench_world(rb, sc, steps, reps, dtype, law="mujoco"):
-    with (rb.World(sc, dtype=dtype) if law == "mujoco" else rb.World(sc, dtype=dtype, law=law)) as w:
+def bench_world(rb, sc, steps, reps, dtype, law="mujoco", **kw):
+    with (rb.World(sc, dtype=dtype, **kw) if law == "mujoco" else rb.World(sc, dtype=dtype, law=law)) as w:
         w.step(steps)                                   # warm-up (captures the step graph)
         rates = []
         for _ in range(reps):
@@ -220,6 +227,8 @@ def main():
                     help="also run every E through the per-environment (ENVS) instance, alternating with the plain run")
     ap.add_argument("--incline-sweep", type=int, default=0, metavar="N",
                     help="N cube-incline angles as one batch against N one-environment batches")
+    ap.add_argument("--box-pile", default="", metavar="NX,NY,LAYERS",
+                    help="scene box_pile(NX, NY, LAYERS), a friction sweep, against one World(max_partners=32)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "batch_bench.json"))
     a = ap.parse_args()
 
@@ -232,7 +241,19 @@ def main():
                version=rbhip.load().rb_version().decode())
     if a.law != "mujoco":
         res["law"] = a.law
-    if a.incline_sweep:
+    if a.box_pile:
+        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep:
+            raise SystemExit("--box-pile: the plain measurement under the default law only")
+        sc = scenes.box_pile(*(int(t) for t in a.box_pile.split(",")))
+        res.update(scene=sc.name, bodies_per_env=sc.n, sweep="friction 0.2 .. 0.8")
+        res["world"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, max_partners=32)
+        res["batch"] = {str(E): bench_batch(rbhip, sc, E, a.steps, a.reps, a.dtype, sweep={"friction": (0.2, 0.8)})
+                        for E in a.envs}
+        res["world_after"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, max_partners=32)
+        w = res["world"]["median"]
+        res["ratio_vs_world"] = {E: dict(median=r["median"] / w, min=r["min"] / w, max=r["max"] / w)
+                                 for E, r in res["batch"].items()}
+    elif a.incline_sweep:
         res.update(scene="cube_incline", bodies_per_env=1, dtype="f64", unit="seconds per run")
         res["incline_sweep"] = bench_incline_sweep(rbhip, a.incline_sweep, a.steps, a.reps)
     elif a.sampled:
