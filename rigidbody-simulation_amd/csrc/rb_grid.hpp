@@ -908,32 +908,59 @@ __device__ __forceinline__ int32_t search_buckets_wide(const StepParams<T> &p, i
 // The body's 2x2x2 buckets are searched by two lanes: lane t of the body wave
 // (role 0) takes the four buckets on the body's own side of the split axis —
 // b[0], its step-start bucket, among them — and lane t of the helper wave
-// (role 1) the four on the neighbour side.  The split keeps x-adjacent heads,
-// which share a 128-byte line, in one wave.  Both waves run this one routine
+// (role 1) the four on the neighbour side, less the far corner b[7], which
+// the body wave takes as its fifth (RB_SHARE_SPLIT below).  The axis keeps
+// x-adjacent heads, which share a 128-byte line, in one wave but for that
+// corner's pair.  Both waves run this one routine
 // (role is wave-uniform, so the selects are scalar).  Each half lists its
-// head ids in its half of the lane's s_cand column (SHARE_HALF rows), tests
+// head ids in its part of the lane's s_cand column (six rows per bucket), tests
 // them and appends its hits unsorted: the body wave fills s_id from row 0 up,
 // the helper from row MAXP - 1 down, and each keeps its first SHARE_HPOS hit
 // snapshots in its half of s_hpos.  Returns the half's hit count (it goes on
-// counting past the rows it may write).  merge_halves then orders the two.
+// counting past the rows it may write).  merge_halves then orders the two,
+// on the helper wave: it ends its search later and holds the body's state, so
+// it finishes the body (rb_step.hpp body_step) and the body wave only searches.
 #ifndef RB_SHARE_AXIS
 #define RB_SHARE_AXIS 1                              // 0: x, 1: y, 2: z
 #endif
 #ifndef RB_SHARE_QBATCH
 #define RB_SHARE_QBATCH 8                            // candidates per round trip (6: C3 12.65 us, 8: 12.51, 12: 12.71)
 #endif
+// buckets the body (search-only) wave takes: 4, the split above; 5: also the
+// far corner b[7] of the helper's side, which then searches three (it is the
+// later wave and finishes the body; this parts the x-adjacent heads 6 and 7).
+// C3 per step, with RB_SHARE_WORK2 (rb_step.hpp) 0 / 1: 4: 12.43 / 12.27 us,
+// 5: 12.46 / 11.99 (profiles/help_finish/variants_ab.log)
+#ifndef RB_SHARE_SPLIT
+#define RB_SHARE_SPLIT 5
+#endif
+// ... of the MAXP 32 instances (worlds made for piles, C4: crowded buckets,
+// long lists): the even split; five lost there, 37.4 -> 39.6 us
+#ifndef RB_SHARE_SPLIT32
+#define RB_SHARE_SPLIT32 4
+#endif
 constexpr int SHARE_BIT = 1 << RB_SHARE_AXIS;
 constexpr int SHARE_QBATCH = RB_SHARE_QBATCH;
-constexpr int SHARE_HALF = WIDE_MAXC / 2;            // head candidates a half lists
+// buckets of role 0 (role 1: the other 8 - na)
+template <int MAXP> constexpr int share_na() { return MAXP > 16 ? RB_SHARE_SPLIT32 : RB_SHARE_SPLIT; }
 constexpr int SHARE_HPOS = WIDE_HPOS / 2;            // hit snapshots a half keeps
 static_assert(RB_SHARE_AXIS == 1 || RB_SHARE_AXIS == 2, "a split along x parts the heads of one line");
+static_assert((RB_SHARE_SPLIT == 4 || RB_SHARE_SPLIT == 5) && (RB_SHARE_SPLIT32 == 4 || RB_SHARE_SPLIT32 == 5),
+              "the body wave searches four or five buckets");
 // own bucket q of a half -> its index among the eight, role 0 (a zero bit put in at the split axis)
 constexpr int share_k0(int q) { return ((q & ~(SHARE_BIT - 1)) << 1) | (q & (SHARE_BIT - 1)); }
+// own bucket q of role r -> its index among the eight (-1: the role has no bucket q); na: role 0's buckets
+constexpr int share_k(int na, int r, int q) {
+    return r == 0 ? (q < 4 ? share_k0(q) : 7) : (q < 8 - na ? share_k0(q) | SHARE_BIT : -1);
+}
 
-template <typename T, int MAXP, bool EP, typename Hit, typename Overlap>
+// overlap() runs under the head loads, under() under the first candidate
+// batch's snapshot loads (every lane issues that batch).
+template <typename T, int MAXP, bool EP, typename Hit, typename Overlap, typename Under>
 __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int32_t i, V3<T> x, int role, int32_t *s_id,
                                                     uint32_t *s_cand, Snap<T> *s_hpos, int tid, uint32_t gen,
-                                                    const Table<T> &cur, uint32_t &b0, Hit hit, Overlap overlap) {
+                                                    const Table<T> &cur, uint32_t &b0, Hit hit, Overlap overlap,
+                                                    Under under) {
     constexpr int NB = STEP_BLOCK;
     constexpr int QB = SHARE_QBATCH;
     int32_t cx = 0, cy = 0, cz = 0, sx = 1, sy = 1, sz = 1;
@@ -941,15 +968,21 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
     // reads valid buckets and counts them as empty)
     const bool ok = neighbourhood(p, x, cx, cy, cz, sx, sy, sz);
     if (!ok && role == 0) atomicOr(p.err, ERR_DOMAIN);
-    uint32_t b[8], bo[4];
-    int32_t c[4];
-    Head6 hd[4];
+    // buckets of role 0, of role 1, slots of the longer share
+    constexpr int NA = share_na<MAXP>(), NBK = 8 - NA, NQ = NA > NBK ? NA : NBK;
+    // this wave's bucket count (wave-uniform; a constant for the even split)
+    const int nq = NA == NBK ? NA : role ? NBK : NA;
+    uint32_t b[8], bo[NQ];
+    int32_t c[NQ];
+    Head6 hd[NQ];
     neighbour_buckets<LAYOUT_LINEAR>(p.grid, cx, cy, cz, sx, sy, sz, b);
     constexpr int rl = 2;                         // heads per line: wide-form worlds 4 (rb_api_world.hip)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        bo[q] = role ? b[share_k0(q) | SHARE_BIT] : b[share_k0(q)];
-        hd[q] = bucket_head6(cur, (uint32_t)CHK(bo[q], p.grid.H), rl);
+    for (int q = 0; q < NQ; ++q) {
+        // (a slot past the wave's share: role 0's bucket, never loaded or listed)
+        bo[q] = role && share_k(NA, 1, q) >= 0 ? b[share_k(NA, 1, q) < 0 ? 0 : share_k(NA, 1, q)] : b[share_k(NA, 0, q)];
+        hd[q] = Head6{uint4{0u, 0u, 0u, 0u}, uint4{0u, 0u, 0u, 0u}};
+        if (q < nq) hd[q] = bucket_head6(cur, (uint32_t)CHK(bo[q], p.grid.H), rl);
     }
     // (an out-of-domain body: cell (0, 0, 0)'s bucket, not NO_BUCKET — it
     // could only make the body skip its claim, and ERR_DOMAIN discards the step)
@@ -957,19 +990,22 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
     __builtin_amdgcn_sched_barrier(0);            // the head loads issue before the helper's work
     overlap();
     STAMP(8);
-    uint32_t *const cand = s_cand + role * (SHARE_HALF * NB) + tid;
+    uint32_t *const cand = s_cand + role * (NA * WIDE_HEAD_IDS * NB) + tid;   // (role 1: the rows after role 0's)
     int32_t n = 0;
     bool more = false;
     uint32_t spm = 0;
     [[maybe_unused]] const uint32_t ng = (uint32_t)p.n_global;   // (search_buckets_wide: appended tables)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NQ; ++q) {
+        c[q] = 0;
+        if (q >= nq) continue;
         int32_t m = ok ? head_count(hd[q].a, gen) : 0;
         // visit once: an equal bucket of a lower index among the eight,
         // whichever wave owns it
+        const int K0 = share_k(NA, 0, q), K1 = share_k(NA, 1, q);   // (constants once the loop is unrolled)
 #pragma unroll
-        for (int j = 0; j < (share_k0(q) | SHARE_BIT); ++j)
-            if ((j < share_k0(q) || role) && b[j] == bo[q]) m = 0;
+        for (int j = 0; j < (K0 > K1 ? K0 : K1); ++j)
+            if (j < (role ? K1 : K0) && b[j] == bo[q]) m = 0;
         c[q] = m;
         more |= m > WIDE_HEAD_IDS;
         if (m > 0 && head_spilled(hd[q].a, gen)) spm |= 1u << q;
@@ -991,7 +1027,7 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
         if (RB_WIDE_LDSPOS && np_ < SHARE_HPOS) kept[np_ * NB] = sn;
         ++np_;
     };
-    auto batch = [&](int base) {
+    auto batch = [&](int base, auto work) {
         uint32_t tj[QB];
         Snap<T> sn[QB];
 #pragma unroll
@@ -1001,19 +1037,20 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
             sn[u] = Snap<T>{x.x, x.y, x.z, T(0)};
             if ((tj[u] & ~BOX_FLAG) != (uint32_t)i) sn[u] = xld(p.snap_cur + CHK(tj[u] & ~BOX_FLAG, p.n_global));
         }
+        work();
 #pragma unroll
         for (int u = 0; u < QB; ++u)
             if (base + u < n && hit(tj[u], sn[u])) append((int32_t)(tj[u] & ~BOX_FLAG), sn[u]);
     };
-    batch(0);
-    for (int base = QB; base < n; base += QB) batch(base);
+    batch(0, under);
+    for (int base = QB; base < n; base += QB) batch(base, [] {});
     STAMP(9);
     if (RB_WIDE_MORE && more) {
-        // buckets of 7+ bodies: as search_buckets_wide's pipelined rare path, over four buckets
-        int32_t E[4];
+        // buckets of 7+ bodies: as search_buckets_wide's pipelined rare path, over this wave's buckets
+        int32_t E[NQ];
         int32_t e = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < NQ; ++q) {
             e += c[q] > WIDE_HEAD_IDS ? c[q] - WIDE_HEAD_IDS : 0;
             E[q] = e;
         }
@@ -1022,10 +1059,10 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
 #pragma unroll
             for (int u = 0; u < QB; ++u) {
                 const int32_t t = t0 + u;
-                uint32_t bk = bo[3];
-                int32_t base = E[2];
+                uint32_t bk = bo[NQ - 1];
+                int32_t base = E[NQ - 2];
 #pragma unroll
-                for (int q = 2; q >= 0; --q)
+                for (int q = NQ - 2; q >= 0; --q)
                     if (t < E[q]) { bk = bo[q]; base = q ? E[q - 1] : 0; }
                 tjn[u] = t < e ? xld(slot_word(cur, bk, t - base + WIDE_HEAD_IDS, rl)) : (uint32_t)i;
             }
@@ -1050,9 +1087,9 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
     }
     if (RB_WIDE_MORE && spm) {                        // rarer: ids past full buckets (indices stashed in the half's rows)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cand[q * NB] = bo[q];
+        for (int q = 0; q < NQ; ++q) cand[q * NB] = bo[q];
 #pragma unroll 1
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < NQ; ++q) {
             if (!((spm >> q) & 1u)) continue;
             spill_scan(cur, gen, cand[q * NB], [&](uint32_t t) {
                 const uint32_t j = t & ~BOX_FLAG;
@@ -1067,8 +1104,9 @@ __device__ __forceinline__ int32_t search_half_wide(const StepParams<T> &p, int3
     return np_;
 }
 
-// The body wave, once both halves are done (after the barriers): the two
-// hit lists (na from row 0 up, nb from row MAXP - 1 down) become one list in
+// The finishing (helper) wave, once both halves are done (after the barrier):
+// the two hit lists (na, the body wave's, from row 0 up; nb, its own, from
+// row MAXP - 1 down) become one list in
 // rows 0.. of s_id, ascending by id, with s_didx mapping each to its kept
 // snapshot's slot (255: not kept) — the orders and the duplicate rule of
 // search_buckets_wide.  The rank sort's scratch is the lane's s_cand column.

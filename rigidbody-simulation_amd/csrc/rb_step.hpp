@@ -46,7 +46,9 @@
         if (k == 0 || k == 6) { /* the constant-rate clock too, comparable across XCDs */            \
             unsigned long long r_;                                                                \
             asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r_)::"memory");        \
-            if (threadIdx.x == 0 && blockIdx.x < (1u << 16)) rb_stamp_buf[blockIdx.x][k == 0 ? 12 : 13] = r_; \
+            /* (each wave in its own buffer: the shared search's second wave is the one that reaches 6) */ \
+            if ((threadIdx.x & 63) == 0 && blockIdx.x < (1u << 16))                               \
+                (threadIdx.x >> 6 ? rb_stamp_buf_help : rb_stamp_buf)[blockIdx.x][k == 0 ? 12 : 13] = r_; \
         }                                                                                         \
     } while (0)
 #else
@@ -294,6 +296,27 @@ template <typename T> struct Lead {
 #ifndef RB_SOLVE_PIPE
 #define RB_SOLVE_PIPE 1
 #endif
+// shared search, the helper wave's own work: 0: all of it under its head
+// loads; 1: inv(I_w) there, gravity and the plane contacts under its first
+// candidate batch
+// (measured with RB_SHARE_SPLIT, rb_grid.hpp: only the two together pay)
+#ifndef RB_SHARE_WORK2
+#define RB_SHARE_WORK2 1
+#endif
+// ... of the MAXP 32 instances (with RB_SHARE_SPLIT32)
+#ifndef RB_SHARE_WORK2_32
+#define RB_SHARE_WORK2_32 0
+#endif
+// shared search: the helper wave finishes the body (merge, solves,
+// integration, insert, the kernel's tail) from its own registers and the body
+// wave only searches.  Not in the MAXP 32 instances — worlds made for piles,
+// C4: there the move alone lost, 37.6 -> 38.4 us per step
+// (profiles/help_finish/variants_c4_ab.log) — which keep the hand-over in
+// LDS to the body wave
+#ifndef RB_SHARE_FINISH32
+#define RB_SHARE_FINISH32 0
+#endif
+template <int MAXP> constexpr bool share_finish() { return MAXP <= 16 || RB_SHARE_FINISH32 != 0; }
 // batches of partner snapshots in flight ahead of the solve (the helper-wave
 // wide form only: its register budget has room for a second batch)
 #ifndef RB_SOLVE_DEPTH
@@ -607,15 +630,32 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     int32_t np_ = 0;
     bool defer = false;                          // a box-involved partner in range: the box kernel steps it
     [[maybe_unused]] int32_t n_half = 0;         // shared search: this wave's hits
+    // what a helper wave has done for the body already (HelpDone)
+    bool help_planes = false;
+    int32_t help_nrec = 0;
+    // shared search: the helper wave finishes the body (below)
+    constexpr bool FIN = SHARE && share_finish<MAXP>();
     if constexpr (SHARE) {
-        // the search shared with the helper wave (rb_grid.hpp
-        // search_half_wide): each wave four of the eight buckets.  The helper
+        // the search shared between the two waves (rb_grid.hpp
+        // search_half_wide): the body wave five of the eight buckets, the helper three.  The helper
         // does its work (help_body's: inv(I_w), gravity, plane contacts)
-        // under its head loads and keeps the results in registers until the
-        // body wave is done with the list area
+        // under its head loads, and, being the later of the two and the one
+        // that holds the body's state in registers, finishes the body: the
+        // body wave (role 0) only searches, leaves its hit count and defer
+        // flag in s_half and is done at the one barrier
         M3<T> hm{};
         int32_t hrec = 0;
         bool hplanes = false;
+        // gravity and the plane contacts (not with applied forces: body_update's)
+        constexpr bool work2 = MAXP > 16 ? RB_SHARE_WORK2_32 != 0 : RB_SHARE_WORK2 != 0;
+        auto own_planes = [&] {
+            if (p.xfrc) return;
+            apply_force(p, l, in.m, invI, in.v, in.w);
+            const T hk = impulse_k(in.m);
+            if (kind == 0) solve_planes_sphere(p, p, l, x, sz.x, in.m, hk, invI, in.v, in.w, hrec);
+            else solve_planes_box(p, p, l, x, mj_body_mat(in.q), sz, in.m, hk, invI, in.v, in.w, hrec);
+            hplanes = true;
+        };
         if (RB_ABLATE != 1 && active)
             n_half = search_half_wide<T, MAXP, EP>(
                 p, i, x, role, s_id, s_cand, s_hpos, tid, gen, cur, b0,
@@ -623,32 +663,58 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
                 [&] {
                     if (!role) return;
                     hm = invI.get();
-                    if (!p.xfrc) {
-                        apply_force(p, l, in.m, invI, in.v, in.w);
-                        const T hk = impulse_k(in.m);
-                        if (kind == 0) solve_planes_sphere(p, p, l, x, sz.x, in.m, hk, invI, in.v, in.w, hrec);
-                        else solve_planes_box(p, p, l, x, mj_body_mat(in.q), sz, in.m, hk, invI, in.v, in.w, hrec);
-                        hplanes = true;
-                    }
+                    if (!work2) own_planes();
+                },
+                [&] {
+                    if (!work2 || !role) return;
+                    __builtin_amdgcn_sched_barrier(0);   // the candidate loads issue before the work
+                    own_planes();
                 });
-        if (role && active) s_half[tid] = (uint32_t)(n_half < 0xffff ? n_half : 0xffff) | (defer ? 1u << 16 : 0u);
+        // the wave that does not finish leaves its hit count and defer flag
+        if ((FIN ? !role : role) && active)
+            s_half[tid] = (uint32_t)(n_half < 0xffff ? n_half : 0xffff) | (defer ? 1u << 16 : 0u);
 #if RB_STAMPS
-        if (role) STAMP(2);                      // the helper's last hit is written
+        if (role) STAMP(2);                      // the helper wave's last hit is written
 #endif
-        __syncthreads();                         // both searches are done with s_cand: the helper fills it
-        if (role && active) {
-            T *o = s_help + tid;
-#pragma unroll
-            for (int e = 0; e < 9; ++e) o[e * NB] = hm.a[e];
-            o[9 * NB] = in.v.x; o[10 * NB] = in.v.y; o[11 * NB] = in.v.z;
-            o[12 * NB] = in.w.x; o[13 * NB] = in.w.y; o[14 * NB] = in.w.z;
-            o[15 * NB] = T(hplanes ? hrec : -1);
-            o[16 * NB] = in.q.w; o[17 * NB] = in.q.x; o[18 * NB] = in.q.y; o[19 * NB] = in.q.z;
-            o[20 * NB] = in.m;
-        }
+        // every lane of both waves, idle ones too: the other wave's hits and
+        // s_half are written, and both searches are done with s_cand (the
+        // merge's scratch)
         __syncthreads();
-        if (role) return;
-        if (active) defer |= (s_half[tid] >> 16) != 0;
+        if constexpr (FIN) {
+#if RB_STAMPS
+            if (role) STAMP(11);                 // the finishing wave is past the barrier
+            else STAMP(2);                       // the search-only wave's wait (10 -> 2) is over
+#endif
+            if (!role) return;
+            if (active) defer |= (s_half[tid] >> 16) != 0;
+            // inv(I_w), the post-gravity, post-plane v and w and the plane
+            // contacts' record count, straight from this wave's registers (with
+            // applied forces: body_update applies the force and solves the planes)
+            invI.m = hm;
+            invI.have = true;
+            forced = hplanes;
+            help_planes = hplanes;
+            help_nrec = hrec;
+        } else {
+            // MAXP 32 instances: the helper hands its results over in the
+            // list area, as help_body does, and the body wave finishes
+            if (role && active) {
+                T *o = s_help + tid;
+#pragma unroll
+                for (int e = 0; e < 9; ++e) o[e * NB] = hm.a[e];
+                o[9 * NB] = in.v.x; o[10 * NB] = in.v.y; o[11 * NB] = in.v.z;
+                o[12 * NB] = in.w.x; o[13 * NB] = in.w.y; o[14 * NB] = in.w.z;
+                o[15 * NB] = T(hplanes ? hrec : -1);
+                o[16 * NB] = in.q.w; o[17 * NB] = in.q.x; o[18 * NB] = in.q.y; o[19 * NB] = in.q.z;
+                o[20 * NB] = in.m;
+            }
+            __syncthreads();
+            if (role) return;
+            if (active) defer |= (s_half[tid] >> 16) != 0;
+#if RB_STAMPS
+            STAMP(2);
+#endif
+        }
     } else if constexpr (G == 1 && WIDE && HELP) {
         // the helper wave evaluates inv(I_w), gravity and the plane contacts
         // (help_body); every lane of the body wave takes part in its two
@@ -686,7 +752,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
                                               }
                                           });
     }
-    STAMP(2);
+    if constexpr (!SHARE) STAMP(2);              // (shared search: stamped at its barrier)
     if (RB_ABLATE == 7) np_ = 0;                 // diagnostic: search, but solve no partner contact
     if (!active || k != 0 || RB_ABLATE == 4) return;
     if (!BOXES && defer) {                       // box worlds only (p.defer_q set)
@@ -701,9 +767,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         invI.I = in.I;
         invI.q = in.q;
     }
-    bool help_planes = false;
-    int32_t help_nrec = 0;
-    if constexpr (HELP) {
+    if constexpr (HELP && !FIN) {
         // the helper's results (its LDS writes precede the search's barriers)
         const T *o = s_help + slot;
         constexpr int NBH = STEP_BLOCK / G;
@@ -726,14 +790,16 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         help_planes = pr >= T(0);
         help_nrec = help_planes ? (int32_t)pr : 0;
     }
-    // shared search: the two halves' hits, merged and ordered (its scratch is
-    // the list area, so after the helper's results are read from it)
+    // shared search: the two halves' hits, merged and ordered by the
+    // finishing wave: the body wave's list (rows 0 up, its count from s_half)
+    // and this wave's own (rows MAXP - 1 down)
     if constexpr (SHARE) {
-        // the results above were read through a T pointer from the area the
-        // merge now writes as uint32 rows: no access may move across this point
+        // the merge's scratch is the candidate list area this wave's search
+        // read last: no access may move across this point
         asm volatile("" ::: "memory");
         if (RB_ABLATE != 1)
-            np_ = merge_halves<T, MAXP, EP>(p, s_id, s_cand, s_didx, tid, n_half, (int32_t)(s_half[tid] & 0xffffu), ep_appended);
+            np_ = FIN ? merge_halves<T, MAXP, EP>(p, s_id, s_cand, s_didx, tid, (int32_t)(s_half[tid] & 0xffffu), n_half, ep_appended)
+                      : merge_halves<T, MAXP, EP>(p, s_id, s_cand, s_didx, tid, n_half, (int32_t)(s_half[tid] & 0xffffu), ep_appended);
         STAMP(7);
         if (RB_ABLATE == 7) np_ = 0;
     }
@@ -843,7 +909,9 @@ __device__ __forceinline__ void help_body(const StepParams<T> &p, const Lead<T> 
 // wide forms — the single-GPU bench's kernels — are also instantiated
 // without it (launch_step_wide picks), which measured 1-2 % faster at C3
 // SHARE: the helper wave of the wide form also searches half of each body's
-// neighbourhood (body_step; rb_grid.hpp search_half_wide)
+// neighbourhood (body_step; rb_grid.hpp search_half_wide) and then finishes
+// the body — merge, solves, integration, insert and this function's tail —
+// from its own registers; the body wave only searches
 template <typename T, int MAXP, int G, bool WIDE = false, bool BOXES = false, bool HELP = false, bool HALO = true,
           bool EP = false, bool SHARE = false>
 __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> &ld) {
@@ -897,7 +965,10 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
         body_step<T, MAXP, G, WIDE, BOXES, true, HELP, EP, SHARE>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos,
                                                               s_cand, cell, 0u /* loaded in body_step */, s_poly, s_didx,
                                                               s_hpos, help_lds, role, s_half);
-    if (SHARE && role) return;                   // the helper wave is done
+    // shared search: the body wave is done; the helper wave, which finished
+    // the bodies, holds their cells and does the rest (its tid 0: block 0's stores)
+    // (MAXP 32 instances: the body wave finishes and the helper is done)
+    if (SHARE && (share_finish<MAXP>() ? !role : role)) return;
     if (p.bounds) fold_bounds(p.bounds, cell);
     if (HALO && p.halo.mail) {                   // halo-exchanging shard: push to the peers
         int32_t b[6];

@@ -44,7 +44,7 @@ void step_kernel_wide(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T
 // the wide form with a helper wave per workgroup (help_body): two waves per
 // SIMD, each within 256 registers
 // SHARE: the helper lanes also search half of each body's 2x2x2
-// neighbourhood (rb_grid.hpp search_half_wide)
+// neighbourhood (rb_grid.hpp search_half_wide) and finish the body
 template <typename T, int MAXP, bool HALO, bool EP, bool SHARE>
 __global__ __launch_bounds__(2 * STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void step_kernel_wide_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,

@@ -8,9 +8,10 @@ builds and RBHIP_HELP_SEARCH settings.  Not part of the product.
         [--variants LABEL=PATH,...]
 
 Without --variants: the parent library (if given), this tree's library with
-the shared search on ("child") and off ("child_off").  With --variants: this
-tree's library and the listed builds (e.g. made with WEXTRA=-DRB_SHARE_QBATCH=6
-and OUT=PATH), all with the shared search on.  flat32k is flat_spheres(256, 128).
+the shared search on ("child") and off ("child_off").  With --variants: the
+parent library (if given), this tree's library and the listed builds (e.g.
+made with WEXTRA=-DRB_SHARE_QBATCH=6 or -DRB_SHARE_SPLIT=5 and OUT=PATH), all
+with the shared search on.  flat32k is flat_spheres(256, 128).
 profiles/help_search/shapes_ab.log and variants_ab.log are its output (the
 parent's library there was built from the parent commit into
 gpu_jobs/parent/librbhip.so, a directory kept out of git).
@@ -39,7 +40,8 @@ def main():
     shapes = [(c, int(w), int(k)) for c, w, k in (s.split(":") for s in a.shapes.split(","))]
     scs = {c: (scenes.flat_spheres(256, 128) if c == "flat32k" else scenes.make(c)) for c, _, _ in shapes}
     if a.variants:
-        variants = [("child", a.lib, "1")] + [tuple(v.split("=", 1)) + ("1",) for v in a.variants.split(",") if v]
+        variants = (([("parent", a.parent, None)] if a.parent else []) + [("child", a.lib, "1")] +
+                    [tuple(v.split("=", 1)) + ("1",) for v in a.variants.split(",") if v])
     else:
         variants = ([("parent", a.parent, None)] if a.parent else []) + [("child", a.lib, "1"), ("child_off", a.lib, "0")]
     res = {}

@@ -2,10 +2,12 @@
 Phases: 0 start | 1 after table clear | 2 after broadphase search |
 3 after state load + gravity | 4 after contact solves | 5 after position
 store + insert | 6 end.  Prints the median / p90 over workgroups.
-Shared search (the wide + helper form, RBHIP_HELP_SEARCH=1): the body wave's
-stamp 2 is taken after the barriers (its search span: 1 -> 10), 7 after the
-merge and sort; the helper wave's stamps (its own buffer) are 0 start |
-1, 8, 9, 10 as the body wave's | 2 its last hit written."""
+Shared search (the wide + helper form, RBHIP_HELP_SEARCH=1): the helper wave
+finishes the body, so the chain 0 .. 6 is the helper wave's (its own buffer):
+0 start | 1, 8, 9, 10 its search | 2 its last hit written | 11 past the
+barrier | 7 after the merge and sort | 3 .. 6 as above.  The body wave only
+searches: 0, 1, 8, 9, 10, and 2 once it is past the barrier (10 -> 2: its
+wait for the helper)."""
 import ctypes, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,21 +23,28 @@ from rbhip import _lib, scenes
 import rbhip.world as W
 L = _lib.load(LIB)
 L.rb_diag_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
-def report_help(kind, buf, hbuf):
-    """The helper wave of the shared search, beside the body wave's search."""
-    if not hbuf[:, 2].any():
-        return
-    i64 = lambda a: a.astype(np.int64)            # noqa: E731
-    body = i64(buf[:, 10]) - i64(buf[:, 1])
-    span = i64(hbuf[:, 2]) - i64(hbuf[:, 0])
-    late = i64(hbuf[:, 2]) - i64(buf[:, 10])
-    print(f"   [{kind}] body wave search (1 -> 10) median {int(np.median(body))} p90 {int(np.percentile(body, 90))}; "
-          f"merge + sort (2 -> 7) median {int(np.median(i64(buf[:, 7]) - i64(buf[:, 2])))}")
-    print(f"   [{kind}] helper wave start -> last hit written median {int(np.median(span))} p90 {int(np.percentile(span, 90))}; "
-          f"helper done after the body wave's search by median {int(np.median(late))} p90 {int(np.percentile(late, 90))}")
-    for a, b_, nm in [(0, 1, "lead"), (1, 8, "snap+heads+work"), (8, 9, "heads+batch1"), (9, 10, "later batches")]:
-        dd = i64(hbuf[:, b_]) - i64(hbuf[:, a])
-        print(f"     helper {nm:16s} median {int(np.median(dd)):8d}  p90 {int(np.percentile(dd, 90)):8d}")
+def report_finish(sc, kind, buf, hbuf):
+    """Shared search: the helper (finishing) wave's chain from its start to
+    its last store, and the body (search-only) wave beside it."""
+    a, h = buf.astype(np.int64), hbuf.astype(np.int64)
+
+    def line(who, t, lo, hi, nm):
+        dd = t[:, hi] - t[:, lo]
+        print(f"     {who} {nm:24s} median {int(np.median(dd)):8d}  p90 {int(np.percentile(dd, 90)):8d}")
+
+    tot = h[:, 6] - h[:, 0]
+    span = h[:, 6].max() - min(h[:, 0].min(), a[:, 0].min())
+    print(f"N={sc.n} [{kind} launch, shared search]: kernel span {int(span)} cyc; finishing wave start -> last store "
+          f"median {int(np.median(tot))} p90 {int(np.percentile(tot, 90))}")
+    for lo, hi, nm in [(0, 1, "lead"), (1, 8, "snap+heads issue+own work"), (8, 9, "heads+batch1"), (9, 10, "later batches"),
+                       (10, 2, "last hit written"), (2, 11, "barrier"), (11, 7, "merge+sort"), (7, 3, "force (applied only)"),
+                       (3, 4, "solves"), (4, 5, "pos+insert"), (5, 6, "quat+store")]:
+        line("finishing", h, lo, hi, nm)
+    for lo, hi, nm in [(0, 1, "lead"), (1, 10, "search"), (10, 2, "wait at the barrier")]:
+        line("search-only", a, lo, hi, nm)
+    late = h[:, 2] - a[:, 10]
+    print(f"     search-only wave done before the finishing wave's last hit by median {int(np.median(late))} "
+          f"p90 {int(np.percentile(late, 90))}")
 
 
 def report(sc, G, kind, buf):
@@ -89,6 +98,7 @@ for nx, ny, warm in sizes:
             if kind == "step" or len(seen) == 2:
                 break
     for kind, (buf, hbuf) in seen.items():
-        report(sc, G, kind, buf)
-        if G == 1:
-            report_help(kind, buf, hbuf)
+        if G == 1 and hbuf[:, 6].any():           # the helper wave reached the end: it finished the bodies
+            report_finish(sc, kind, buf, hbuf)
+        else:
+            report(sc, G, kind, buf)
