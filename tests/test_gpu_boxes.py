@@ -7,6 +7,8 @@ restatement."""
 import numpy as np
 import pytest
 
+from box_geometry import random as _random_pairs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -20,25 +22,6 @@ def rb():
 def _same(a, b):
     return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64),
                                                  np.ascontiguousarray(b).view(np.uint64))
-
-
-def _random_pairs(n, seed=0):
-    rng = np.random.default_rng(seed)
-    rows = []
-    for _ in range(n):
-        k1, k2 = rng.integers(0, 2, 2)
-        q1, q2 = rng.normal(size=4), rng.normal(size=4)
-        s1 = [.1, 0, 0] if k1 == 0 else list(rng.uniform(.1, .5, 3))
-        s2 = [.1, 0, 0] if k2 == 0 else list(rng.uniform(.1, .5, 3))
-        c2 = rng.uniform(-.8, .8, 3)
-        if rng.random() < 0.1:
-            c2 = rng.uniform(-.05, .05, 3)             # deep: sphere centre inside the box
-        rows.append([k1, k2, 0, 0, 0, *(q1 / np.linalg.norm(q1)), *s1, *c2, *(q2 / np.linalg.norm(q2)), *s2])
-    # axis-aligned stacks: parallel edges (skipped axes) and face-face clipping
-    for dz in (0.79, 0.7, 0.5):
-        for dx in (0.0, 0.3, 0.6):
-            rows.append([1, 1, 0, 0, 0, 1, 0, 0, 0, .4, .4, .4, dx, 0.1, dz, 1, 0, 0, 0, .4, .4, .4])
-    return np.array(rows, float)
 
 
 def test_kat_narrow_device_bit_exact(rb, oracle):

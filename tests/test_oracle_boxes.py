@@ -8,6 +8,8 @@ same oracle bit for bit in tests/test_gpu_boxes.py."""
 import numpy as np
 import pytest
 
+from box_geometry import random as random_pairs
+
 I = [1.0, 0.0, 0.0, 0.0]
 SPHERE, BOX = 0, 1
 
@@ -71,16 +73,8 @@ def test_edge_edge(oracle):
 
 
 def test_separated_and_random_pairs_are_finite(oracle):
-    rng = np.random.default_rng(0)
-    rows = []
-    for _ in range(3000):
-        k1, k2 = rng.integers(0, 2, 2)
-        q1, q2 = rng.normal(size=4), rng.normal(size=4)
-        s1 = [.1, 0, 0] if k1 == 0 else list(rng.uniform(.1, .5, 3))
-        s2 = [.1, 0, 0] if k2 == 0 else list(rng.uniform(.1, .5, 3))
-        rows.append(row(k1, [0, 0, 0], q1 / np.linalg.norm(q1), s1, k2, rng.uniform(-.8, .8, 3),
-                        q2 / np.linalg.norm(q2), s2))
-    out = oracle.kat_narrow(np.array(rows))
+    rows = random_pairs(3000, seed=0)
+    out = oracle.kat_narrow(rows)
     assert np.isfinite(out).all()
     n = out[:, 0].astype(int)
     assert n.max() <= 4 and (n > 0).sum() > 300
