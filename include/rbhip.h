@@ -346,11 +346,12 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * An environment steps bit-identically to an rb_world of the same scene,
  * under either contact law (rb_batch_set_contact_law).
  * Arrays are environment-major: body k of environment e at row e*M + k.
- * Not covered (use rb_world): contact recording, caller streams and
- * asynchronous stepping, sharding, per-environment kinds or plane
- * counts, more than 64 bodies per environment; under RB_LAW_BALLS also
- * per-environment planes and applied forces.
- * A batch handle is not thread-safe; every call is synchronous.
+ * Not covered (use rb_world): contact recording, sharding,
+ * per-environment kinds or plane counts, more than 64 bodies per
+ * environment; under RB_LAW_BALLS also per-environment planes and applied
+ * forces.
+ * A batch handle is not thread-safe; every call that takes host arrays is
+ * synchronous (the device-resident boundary below only enqueues).
  *
  * A step launch runs at most RB_BATCH_CHUNK steps (a bound on kernel duration
  * on a shared device); longer runs are several launches, with the same
@@ -477,6 +478,68 @@ int  rb_batch_set_gravity(rb_batch *b, const double *gravity);
  * array, and rb_batch_set_contact_law(RB_LAW_BALLS) while either is set,
  * return RB_EUNSUPPORTED and change nothing. */
 int  rb_batch_set_xfrc(rb_batch *b, const double *xfrc);
+
+/* ---- the device-resident boundary of a batch (additive to librbhip 0.4) ----
+ * The state, the applied forces and the samples of a batch in device memory
+ * of the caller, on a stream of the caller: a closed loop (read the state,
+ * compute data.xfrc_applied from it, collision.py:66-70, step, reset the
+ * environments that are done) without a download, an upload or a host
+ * synchronisation per iteration.  io_dtype (RB_F64 | RB_F32) is the element
+ * type of the caller's arrays, whatever the batch's real type; conversion is a
+ * C cast.  Layouts are those of the host calls: [n_envs][M][7] qpos,
+ * [n_envs][M][6] qvel and xfrc.  Every array must be device memory on the
+ * batch's device (checked on the host): a host pointer, or memory of another
+ * device, is RB_EINVAL with nothing enqueued.  Every call below except
+ * rb_batch_sync enqueues on the batch's stream and returns without waiting;
+ * argument errors are returned at once and a refused call changes nothing.
+ * Stepping a batch under a stream capture of the caller (hipGraph,
+ * torch.cuda.graph) is not supported and not attempted.
+ *
+ * rb_batch_set_stream: as rb_set_stream for a world.  Waits for the work on
+ * the old stream; all later work of the batch, the synchronous entries above
+ * included, is enqueued on hip_stream (a hipStream_t; NULL = the null stream).
+ * The batch keeps its own stream and destroys only that one. */
+int  rb_batch_set_stream(rb_batch *b, void *hip_stream);
+/* The launches of rb_batch_step, without its report (arguments checked alike). */
+int  rb_batch_step_async(rb_batch *b, int64_t nsteps, double dt, double restitution,
+                         double friction, double contact_threshold);
+/* Waits for the batch's stream, then reports as rb_batch_step: *n_failed =
+ * environments failed so far, or RB_EDOM with n_failed == NULL.  Also reports
+ * and clears a refused rb_batch_set_xfrc_dev (below): RB_EINVAL, the message
+ * naming the environment and the body (*n_failed is still written). */
+int  rb_batch_sync(rb_batch *b, int64_t *n_failed);
+/* rb_batch_set_state from full-size device arrays.  mask [n_envs] bytes on the
+ * device (NULL = all): where mask[e] != 0, environment e's state and snapshot
+ * are written and its status and step count cleared (the per-environment
+ * reset), in one kernel; the rows of other environments are not read. */
+int  rb_batch_set_state_dev(rb_batch *b, const uint8_t *mask, const void *qpos,
+                            const void *qvel, int32_t io_dtype);
+/* All environments; either output may be NULL, not both. */
+int  rb_batch_get_state_dev(rb_batch *b, void *qpos, void *qvel, int32_t io_dtype);
+/* rb_batch_set_xfrc from a device array (RB_EUNSUPPORTED under RB_LAW_BALLS).
+ * The host cannot see the values, so a non-finite one is refused on the
+ * device: the upload writes nothing, the rows keep their earlier contents
+ * (zeros before the first upload), and the next rb_batch_sync returns
+ * RB_EINVAL.  Until that rb_batch_sync, later uploads write nothing either.
+ * The wrinkle: the call itself returns RB_OK, and from it on the batch counts
+ * as having applied forces set (steps launch the per-environment instances;
+ * all-zero rows matter for the sign of zeros) whether or not the upload was
+ * refused; rb_batch_set_xfrc(b, NULL) clears that, as ever.  The synchronous
+ * entries neither report nor clear a refusal. */
+int  rb_batch_set_xfrc_dev(rb_batch *b, const void *xfrc, int32_t io_dtype);
+/* rb_batch_status into device arrays; either may be NULL, not both. */
+int  rb_batch_status_dev(rb_batch *b, int32_t *code, int64_t *steps_done);
+/* rb_batch_run_sampled with the samples written into device arrays of the
+ * caller, qpos [S][n_envs][M][7] and qvel [S][n_envs][M][6] (NULL: positions
+ * and quaternions only), by a transpose kernel per drain of the sample
+ * buffer: no host synchronisation between launches, no copy.  The buffer
+ * holds the slots alone, n_envs * M * rows * sizeof(real) bytes per sample
+ * (rows = 13, or 7), under the same RBHIP_BATCH_SAMPLE_BYTES bound.  Final
+ * state, status and steps_done are those of rb_batch_step(nsteps); no
+ * report (rb_batch_sync).  RB_EINVAL as rb_batch_run_sampled. */
+int  rb_batch_run_sampled_dev(rb_batch *b, int64_t nsteps, int64_t every, double dt,
+                              double restitution, double friction, double contact_threshold,
+                              void *qpos, void *qvel, int32_t io_dtype);
 
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do

@@ -1,9 +1,13 @@
 // rb_api_batch.hip — batched worlds (rb_batch_*; kernels in rb_batch.hip).
 // E replicas of a template environment of M <= 64 bodies, body b of
 // environment e at slot e * M + b of every device row.  All work is enqueued
-// on the batch's own stream; every entry point returns after it finished.
+// on the batch's stream (its own, or the caller's: rb_batch_set_stream); the
+// entries that take host arrays return after it finished, the device-resident
+// boundary (rb_batch_step_async, rb_batch_*_dev; kernels in rb_batch_dev.hip)
+// only enqueues and rb_batch_sync waits.
 #include <cmath>
 
+#include "rb_batch_dev.hpp"
 #include "rb_host.hpp"
 #include "rb_sampleplan.hpp"
 
@@ -13,7 +17,8 @@ static_assert(BATCH_EDOM == RB_EDOM && BATCH_CHUNK == RB_BATCH_CHUNK, "batch con
 
 struct rb_batch {
     int dtype = RB_F64, esz = 8, device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;      // where the batch's work is enqueued: own_stream, or the caller's
+    hipStream_t own_stream = nullptr;  // created with the batch, destroyed with it
     int64_t E = 0, N = 0;              // environments, body slots (E * M)
     int32_t M = 0, n_planes = 0, oriented = 1;
     bool box = false;                  // the template is one box
@@ -47,6 +52,9 @@ struct rb_batch {
     char *samp = nullptr;
     size_t samp_bytes = 0;                      // allocated
     size_t samp_limit = (size_t)256 << 20;      // RBHIP_BATCH_SAMPLE_BYTES
+    // rb_batch_set_xfrc_dev: the smallest body slot an upload was refused for
+    // (DEV_NO_SLOT: none), sticky until rb_batch_sync reports and clears it
+    uint32_t *refused = nullptr;
 };
 
 namespace {
@@ -54,12 +62,12 @@ namespace {
 void free_batch(rb_batch *b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->own_stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind};
+                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
+    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);   // (never the caller's)
     delete b;
 }
 
@@ -238,6 +246,73 @@ int batch_check_ids(const rb_batch *b, const int64_t *env_ids, int64_t n) {
     return RB_OK;
 }
 
+// nsteps steps in launches of at most RB_BATCH_CHUNK steps: the state between
+// two of them is the state between two steps, so the cut changes nothing
+int batch_enqueue_steps(rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr) {
+    for (int64_t left = nsteps; left > 0; left -= BATCH_CHUNK) {
+        const int32_t k = (int32_t)std::min<int64_t>(left, BATCH_CHUNK);
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            return batch_launch<T>(b, batch_params<T>(b, k, dt, e, mu, thr), false);
+        }));
+    }
+    return RB_OK;
+}
+
+// launch l of a sampled run's plan, recording into the `fit` slots of `rows` rows at `slots`
+int batch_enqueue_sampled(rb_batch *b, const SampleLaunch &l, char *slots, int64_t fit, int rows, int64_t every,
+                          double dt, double e, double mu, double thr) {
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        BatchParams<T> p = batch_params<T>(b, (int32_t)l.steps, dt, e, mu, thr);
+        if (l.samples == 0)          // nothing to record in this launch: the plain instance
+            return batch_launch<T>(b, p, false);
+        p.samp = reinterpret_cast<T *>(slots);
+        // phase and period travel as int32: a period past the chunk never samples
+        // inside a launch that does not end on it, so it is clamped per launch
+        p.every = (int32_t)std::min<int64_t>(every, BATCH_CHUNK + 1);   // (a second sample lies past the launch)
+        p.phase = (int32_t)l.phase;                                     // (<= steps <= RB_BATCH_CHUNK here)
+        p.samp_first = (int32_t)l.first;
+        p.samp_slots = (int32_t)fit;
+        p.samp_rows = rows;
+        return batch_launch<T>(b, p, true);
+    }));
+    return RB_OK;
+}
+
+// the sample buffer for `fit` samples of `per` bytes each (it only grows)
+int batch_sample_buffer(rb_batch *b, size_t per, int64_t fit) {
+    const size_t need = per * (size_t)fit;
+    if (need > b->samp_bytes) {
+        if (b->samp) { HIPCHK(hipFree(b->samp)); b->samp = nullptr; }
+        b->samp_bytes = 0;
+        HIPCHK(hipMalloc((void **)&b->samp, need));
+        b->samp_bytes = need;
+    }
+    return RB_OK;
+}
+
+// ---- the device-resident boundary ---------------------------------------------
+template <typename T> DevState<T> batch_dev(rb_batch *b) {
+    return DevState<T>{dp<Snap<T>>(b->snap, 0), BodyState<T>{dp<T>(b->state, 0), b->N}, dp<T>(b->consts, 7 * b->N),
+                       b->code, b->steps_done, b->N, b->M};
+}
+
+int batch_check_io(int32_t io_dtype) {
+    return io_dtype == RB_F64 || io_dtype == RB_F32 ? RB_OK : fail(RB_EINVAL, "io_dtype must be RB_F64 or RB_F32");
+}
+
+// a caller's array: device memory on the batch's device (a refusal leaves no HIP error behind)
+int batch_dev_ptr(const rb_batch *b, const void *p, const char *name) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(RB_EINVAL, "%s is not device memory (a host pointer?)", name);
+    }
+    if (a.device != b->device) return fail(RB_EINVAL, "%s is memory of device %d, the batch is on device %d", name, a.device, b->device);
+    return RB_OK;
+}
+
 // rb_batch_create / rb_batch_create_mixed (mixed: a box among several bodies is accepted)
 int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mixed) {
     if (!out || !d) return fail(RB_EINVAL, "null argument");
@@ -284,8 +359,9 @@ int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mi
         if (atoll(ev) > 0) b->samp_limit = (size_t)atoll(ev);
     auto bail = [&](int rc) { free_batch(b); return rc; };
     if (hipSetDevice(b->device) != hipSuccess) return bail(fail(RB_ENODEV, "hipSetDevice(%d) failed", b->device));
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+    if (hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking) != hipSuccess)
         return bail(fail(RB_ENODEV, "hipStreamCreate failed"));
+    b->stream = b->own_stream;
     const size_t esz = (size_t)b->esz, N = (size_t)b->N, E = (size_t)b->E;
     const std::pair<void **, size_t> allocs[] = {
         {&b->snap, esz * 4 * N}, {&b->state, esz * 13 * N}, {&b->consts, esz * 8 * N},
@@ -295,6 +371,9 @@ int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mi
         if (hipMalloc(a.first, a.second) != hipSuccess) return bail(fail(RB_ENOMEM, "hipMalloc(%zu) failed", a.second));
         if (hipMemsetAsync(*a.first, 0, a.second, b->stream) != hipSuccess) return bail(fail(RB_ENODEV, "hipMemsetAsync failed"));
     }
+    if (hipMalloc((void **)&b->refused, sizeof(uint32_t)) != hipSuccess) return bail(fail(RB_ENOMEM, "hipMalloc(4) failed"));
+    if (hipMemsetAsync(b->refused, 0xff, sizeof(uint32_t), b->stream) != hipSuccess)
+        return bail(fail(RB_ENODEV, "hipMemsetAsync failed"));
     if (b->mixed) {
         const size_t kb = sizeof(int32_t) * (size_t)b->M;
         if (hipMalloc((void **)&b->d_kind, kb) != hipSuccess) return bail(fail(RB_ENOMEM, "hipMalloc(%zu) failed", kb));
@@ -491,15 +570,7 @@ int rb_batch_step(rb_batch *b, int64_t nsteps, double dt, double e, double mu, d
     ApiScope api_scope_(b ? b->device : -1);
     WCHK(batch_check_step(b, nsteps, dt, e, mu, thr));
     HIPCHK(hipSetDevice(b->device));
-    // launches of at most RB_BATCH_CHUNK steps: the state between two of them
-    // is the state between two steps, so the cut changes nothing
-    for (int64_t left = nsteps; left > 0; left -= BATCH_CHUNK) {
-        const int32_t k = (int32_t)std::min<int64_t>(left, BATCH_CHUNK);
-        HIPCHK(by_real(b->dtype, [&](auto t) {
-            using T = decltype(t);
-            return batch_launch<T>(b, batch_params<T>(b, k, dt, e, mu, thr), false);
-        }));
-    }
+    WCHK(batch_enqueue_steps(b, nsteps, dt, e, mu, thr));
     return batch_report(b, n_failed);
 }
 
@@ -511,8 +582,6 @@ int rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, 
     const int64_t S = nsteps / every;
     if (S > 0 && !qpos) return fail(RB_EINVAL, "qpos NULL with %lld samples to record", (long long)S);
     HIPCHK(hipSetDevice(b->device));
-    // phase and period travel as int32: a period past the chunk never samples
-    // inside a launch that does not end on it, so it is clamped per launch below
     const int rows = qvel ? 13 : 7;
     const size_t per = sample_bytes(b, rows);
     int64_t fit = 1;
@@ -522,13 +591,7 @@ int rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, 
                                    "RBHIP_BATCH_SAMPLE_BYTES)", per, b->samp_limit);
         // no more slots than a launch index can address, than fit the bound, than the run needs
         fit = std::min<int64_t>({S, (int64_t)(b->samp_limit / per), (int64_t)INT32_MAX / 2});
-        const size_t need = per * (size_t)fit;
-        if (need > b->samp_bytes) {
-            if (b->samp) { HIPCHK(hipFree(b->samp)); b->samp = nullptr; }
-            b->samp_bytes = 0;
-            HIPCHK(hipMalloc((void **)&b->samp, need));
-            b->samp_bytes = need;
-        }
+        WCHK(batch_sample_buffer(b, per, fit));
     }
     // the slots first, the boundary rows of `fit` samples behind them
     const size_t N = (size_t)b->N;
@@ -539,19 +602,7 @@ int rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, 
     SamplePlan plan(nsteps, every, BATCH_CHUNK, fit);
     SampleLaunch l;
     while (plan.next(l)) {
-        HIPCHK(by_real(b->dtype, [&](auto t) {
-            using T = decltype(t);
-            BatchParams<T> p = batch_params<T>(b, (int32_t)l.steps, dt, e, mu, thr);
-            if (l.samples == 0)          // nothing to record in this launch: the plain instance
-                return batch_launch<T>(b, p, false);
-            p.samp = reinterpret_cast<T *>(slots);
-            p.every = (int32_t)std::min<int64_t>(every, BATCH_CHUNK + 1);   // (a second sample lies past the launch)
-            p.phase = (int32_t)l.phase;                                     // (<= steps <= RB_BATCH_CHUNK here)
-            p.samp_first = (int32_t)l.first;
-            p.samp_slots = (int32_t)fit;
-            p.samp_rows = rows;
-            return batch_launch<T>(b, p, true);
-        }));
+        WCHK(batch_enqueue_sampled(b, l, slots, fit, rows, every, dt, e, mu, thr));
         if (l.drain == 0) continue;
         // a plain synchronous drain: transpose, download, wait
         HIPCHK(by_real(b->dtype, [&](auto t) {
@@ -575,6 +626,166 @@ int rb_batch_status(rb_batch *b, int32_t *code, int64_t *steps_done) {
     if (steps_done)
         HIPCHK(hipMemcpyAsync(steps_done, b->steps_done, sizeof(int64_t) * (size_t)b->E, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
+    return RB_OK;
+}
+
+// ---- the device-resident boundary: everything below but rb_batch_sync only enqueues ----
+
+int rb_batch_set_stream(rb_batch *b, void *s) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    // work queued on the old stream finishes there before later work is ordered on the new one
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->stream = (hipStream_t)s;        // NULL = HIP's null stream
+    return RB_OK;
+}
+
+int rb_batch_step_async(rb_batch *b, int64_t nsteps, double dt, double e, double mu, double thr) {
+    ApiScope api_scope_(b ? b->device : -1);
+    WCHK(batch_check_step(b, nsteps, dt, e, mu, thr));
+    HIPCHK(hipSetDevice(b->device));
+    return batch_enqueue_steps(b, nsteps, dt, e, mu, thr);
+}
+
+int rb_batch_sync(rb_batch *b, int64_t *n_failed) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    // the refusal word of rb_batch_set_xfrc_dev: read and cleared, in stream order
+    uint32_t slot = DEV_NO_SLOT;
+    HIPCHK(hipMemcpyAsync(&slot, b->refused, sizeof(slot), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemsetAsync(b->refused, 0xff, sizeof(slot), b->stream));
+    const int rc = batch_report(b, n_failed);      // (waits for the stream)
+    if (rc != RB_OK && rc != RB_EDOM) return rc;
+    if (slot != DEV_NO_SLOT)
+        return fail(RB_EINVAL, "rb_batch_set_xfrc_dev: environment %lld, body %lld: non-finite applied force or torque "
+                               "(that upload and every later one up to this call wrote nothing)",
+                    (long long)(slot / (uint32_t)b->M), (long long)(slot % (uint32_t)b->M));
+    return rc;
+}
+
+int rb_batch_set_state_dev(rb_batch *b, const uint8_t *mask, const void *qpos, const void *qvel, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (!qpos || !qvel) return fail(RB_EINVAL, "null argument");
+    WCHK(batch_check_io(io_dtype));
+    HIPCHK(hipSetDevice(b->device));
+    if (mask) WCHK(batch_dev_ptr(b, mask, "mask"));
+    WCHK(batch_dev_ptr(b, qpos, "qpos"));
+    WCHK(batch_dev_ptr(b, qvel, "qvel"));
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return by_real(io_dtype, [&](auto io) {
+            using IO = decltype(io);
+            return launch_dev_state_in<T, IO>(batch_dev<T>(b), mask, (const IO *)qpos, (const IO *)qvel, b->stream);
+        });
+    }));
+    return RB_OK;
+}
+
+int rb_batch_get_state_dev(rb_batch *b, void *qpos, void *qvel, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (!qpos && !qvel) return fail(RB_EINVAL, "null argument");
+    WCHK(batch_check_io(io_dtype));
+    HIPCHK(hipSetDevice(b->device));
+    if (qpos) WCHK(batch_dev_ptr(b, qpos, "qpos"));
+    if (qvel) WCHK(batch_dev_ptr(b, qvel, "qvel"));
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return by_real(io_dtype, [&](auto io) {
+            using IO = decltype(io);
+            return launch_dev_state_out<T, IO>(batch_dev<T>(b), (IO *)qpos, (IO *)qvel, b->stream);
+        });
+    }));
+    return RB_OK;
+}
+
+int rb_batch_set_xfrc_dev(rb_batch *b, const void *xfrc, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (!xfrc) return fail(RB_EINVAL, "xfrc NULL (rb_batch_set_xfrc(b, NULL) clears the applied forces)");
+    WCHK(batch_check_io(io_dtype));
+    if (b->law == RB_LAW_BALLS)
+        return fail(RB_EUNSUPPORTED, "the two-ball law takes no applied forces (ball_collision.py:73-125)");
+    HIPCHK(hipSetDevice(b->device));
+    WCHK(batch_dev_ptr(b, xfrc, "xfrc"));
+    if (!b->env_xfrc) {
+        const size_t bytes = (size_t)b->N * 6 * (size_t)b->esz;
+        void *rows = nullptr;
+        HIPCHK(hipMalloc(&rows, bytes));
+        b->env_xfrc = rows;
+        HIPCHK(hipMemsetAsync(rows, 0, bytes, b->stream));
+    }
+    // the host cannot see the check's outcome: forces count as set from here on
+    b->have_xfrc = true;
+    HIPCHK(by_real(io_dtype, [&](auto io) {
+        using IO = decltype(io);
+        return launch_dev_xfrc_check<IO>((const IO *)xfrc, b->N, b->refused, b->stream);
+    }));
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return by_real(io_dtype, [&](auto io) {
+            using IO = decltype(io);
+            return launch_dev_xfrc_in<T, IO>((const IO *)xfrc, dp<T>(b->env_xfrc, 0), b->N, b->refused, b->stream);
+        });
+    }));
+    return RB_OK;
+}
+
+int rb_batch_status_dev(rb_batch *b, int32_t *code, int64_t *steps_done) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (!code && !steps_done) return fail(RB_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(b->device));
+    if (code) WCHK(batch_dev_ptr(b, code, "code"));
+    if (steps_done) WCHK(batch_dev_ptr(b, steps_done, "steps_done"));
+    if (code) HIPCHK(hipMemcpyAsync(code, b->code, sizeof(int32_t) * (size_t)b->E, hipMemcpyDeviceToDevice, b->stream));
+    if (steps_done)
+        HIPCHK(hipMemcpyAsync(steps_done, b->steps_done, sizeof(int64_t) * (size_t)b->E, hipMemcpyDeviceToDevice, b->stream));
+    return RB_OK;
+}
+
+int rb_batch_run_sampled_dev(rb_batch *b, int64_t nsteps, int64_t every, double dt, double e, double mu, double thr,
+                             void *qpos, void *qvel, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    WCHK(batch_check_step(b, nsteps, dt, e, mu, thr));
+    if (every < 1) return fail(RB_EINVAL, "every must be >= 1");
+    WCHK(batch_check_io(io_dtype));
+    const int64_t S = nsteps / every;
+    if (S > 0 && !qpos) return fail(RB_EINVAL, "qpos NULL with %lld samples to record", (long long)S);
+    HIPCHK(hipSetDevice(b->device));
+    const int rows = qvel ? 13 : 7;
+    // the buffer holds the slots alone: the drain writes the caller's arrays
+    const size_t per = (size_t)b->N * (size_t)rows * (size_t)b->esz;
+    int64_t fit = 1;
+    if (S > 0) {
+        WCHK(batch_dev_ptr(b, qpos, "qpos"));
+        if (qvel) WCHK(batch_dev_ptr(b, qvel, "qvel"));
+        if (per > b->samp_limit)
+            return fail(RB_EINVAL, "one sample of the batch (%zu bytes) does not fit the sample buffer (%zu bytes: "
+                                   "RBHIP_BATCH_SAMPLE_BYTES)", per, b->samp_limit);
+        fit = std::min<int64_t>({S, (int64_t)(b->samp_limit / per), (int64_t)INT32_MAX / 2});
+        WCHK(batch_sample_buffer(b, per, fit));
+    }
+    const size_t N = (size_t)b->N;
+    SamplePlan plan(nsteps, every, BATCH_CHUNK, fit);
+    SampleLaunch l;
+    while (plan.next(l)) {
+        WCHK(batch_enqueue_sampled(b, l, b->samp, fit, rows, every, dt, e, mu, thr));
+        if (l.drain == 0) continue;
+        // the drain: one transpose from the slots into the caller's arrays, in stream order
+        const size_t at = (size_t)l.drain_at * N;
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            return by_real(io_dtype, [&](auto io) {
+                using IO = decltype(io);
+                return launch_dev_samples_out<T, IO>(reinterpret_cast<const T *>(b->samp), (int32_t)l.drain, rows, b->N,
+                                                     (IO *)qpos + 7 * at, qvel ? (IO *)qvel + 6 * at : nullptr, b->stream);
+            });
+        }));
+    }
     return RB_OK;
 }
 

@@ -90,6 +90,14 @@ SIGNATURES = {
     "rb_batch_set_planes": (C.c_int, [_P, _P]),
     "rb_batch_set_gravity": (C.c_int, [_P, _P]),
     "rb_batch_set_xfrc": (C.c_int, [_P, _P]),
+    "rb_batch_set_stream": (C.c_int, [_P, _P]),
+    "rb_batch_step_async": (C.c_int, [_P, _I64, _D, _D, _D, _D]),
+    "rb_batch_sync": (C.c_int, [_P, C.POINTER(_I64)]),
+    "rb_batch_set_state_dev": (C.c_int, [_P, _P, _P, _P, _I32]),
+    "rb_batch_get_state_dev": (C.c_int, [_P, _P, _P, _I32]),
+    "rb_batch_set_xfrc_dev": (C.c_int, [_P, _P, _I32]),
+    "rb_batch_status_dev": (C.c_int, [_P, _P, _P]),
+    "rb_batch_run_sampled_dev": (C.c_int, [_P, _I64, _I64, _D, _D, _D, _D, _P, _P, _I32]),
 }
 
 # rb_world_stats indices (include/rbhip.h RB_STAT_*)

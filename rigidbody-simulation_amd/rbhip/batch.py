@@ -15,6 +15,10 @@ included; from_scenes over a list of seeds is an ensemble of piles.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
 multi_sphere_logger.py), one per environment, sampled on the device.
+
+The *_device methods keep all of that in device memory: they take any object
+with __cuda_array_interface__ (a torch tensor on the batch's GPU), enqueue on
+the batch's stream (use_stream) and return without waiting; sync() waits.
 """
 from __future__ import annotations
 
@@ -25,6 +29,40 @@ import numpy as np
 
 from . import _lib
 from .scenes import Scene
+
+
+_IO_CODES = {"<f8": _lib.RB_F64, "<f4": _lib.RB_F32}
+_IO_NAMES = {"f64": "<f8", "f32": "<f4", "float64": "<f8", "float32": "<f4",
+             "torch.float64": "<f8", "torch.float32": "<f4"}
+
+
+def _device_array(name, a, shape, typestrs, out=False):
+    """The device pointer and typestr of argument `name`, an object with
+    __cuda_array_interface__: C-contiguous (strides None), of exactly `shape`,
+    its typestr one of `typestrs`, writable if `out`.  ValueError / TypeError
+    naming the argument otherwise (a numpy array or a CPU tensor included)."""
+    try:
+        cai = a.__cuda_array_interface__
+    except Exception as exc:        # (torch raises TypeError from the attribute of a CPU tensor)
+        raise TypeError(f"{name}: expected device memory (an object with __cuda_array_interface__, such as a "
+                        f"torch tensor on the batch's GPU), got {type(a).__name__}") from exc
+    if tuple(cai["shape"]) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(cai['shape'])}, expected {tuple(shape)}")
+    if cai["typestr"] not in typestrs:
+        raise TypeError(f"{name}: typestr {cai['typestr']!r}, expected one of {', '.join(typestrs)}")
+    if cai.get("strides") is not None:
+        raise ValueError(f"{name}: not C-contiguous (strides {cai['strides']})")
+    ptr, readonly = cai["data"]
+    if out and readonly:
+        raise ValueError(f"{name}: read-only memory given for an output")
+    return (C.c_void_p(ptr) if ptr else None), cai["typestr"]
+
+
+def _io_typestr(name, dtype):
+    ts = _IO_NAMES.get(str(dtype))
+    if ts is None:
+        raise ValueError(f"{name}: {dtype!r} is not 'f64' or 'f32'")
+    return ts
 
 
 class BatchWorld:
@@ -42,6 +80,7 @@ class BatchWorld:
         self.scene = scene
         self.dtype = dtype
         self.n_envs, self.n_bodies = int(n_envs), scene.n
+        self.device = device
         nc = normal_convention or scene.normal_convention
         kind = np.ascontiguousarray(scene.kind, np.int32)
         mass = np.ascontiguousarray(scene.mass, np.float64)
@@ -245,3 +284,117 @@ class BatchWorld:
         done = np.zeros(self.n_envs, np.int64)
         _lib.check(self._L.rb_batch_status(self._h, _lib.ptr(code), _lib.ptr(done)), "rb_batch_status")
         return code, done
+
+    # ---- the device-resident boundary ---------------------------------------
+    # Arrays are objects with __cuda_array_interface__ on the batch's device,
+    # float64 or float32 whatever the batch's dtype (converted by a cast).
+    # Every method but sync() enqueues on the batch's stream and returns.
+    def use_stream(self, handle):
+        """All later work of the batch goes to the HIP stream `handle` (an
+        integer; None or 0: the null stream), after the work on the old one
+        finished.  use_stream(torch.cuda.current_stream().cuda_stream) makes
+        torch's allocator and the batch agree; the stream stays the caller's."""
+        _lib.check(self._L.rb_batch_set_stream(self._h, C.c_void_p(int(handle)) if handle else None),
+                   "rb_batch_set_stream")
+
+    def step_async(self, nsteps: int = 1, dt=None, restitution=None, friction=None, threshold=None):
+        """step() without the wait and the report (sync())."""
+        p = self._params(dt, restitution, friction, threshold)
+        _lib.check(self._L.rb_batch_step_async(self._h, int(nsteps), *p), "rb_batch_step_async")
+
+    def sync(self) -> int:
+        """Wait for the batch's stream; returns how many environments have
+        failed so far.  Raises RbError (EINVAL) naming the environment and the
+        body if a set_xfrc_device() since the last sync() held a non-finite
+        value: that upload wrote nothing."""
+        nf = C.c_int64()
+        _lib.check(self._L.rb_batch_sync(self._h, C.byref(nf)), "rb_batch_sync")
+        return nf.value
+
+    def _pair_typestr(self, names, arrays, dtype):
+        """The one typestr of the given arrays (and dtype, if given); the batch's own if none."""
+        ts = None if dtype is None else _io_typestr("dtype", dtype)
+        for name, a in zip(names, arrays):
+            if a is None:
+                continue
+            try:
+                t = a.__cuda_array_interface__["typestr"]
+            except Exception:       # (not device memory: _device_array says so, naming the argument)
+                t = None
+            if t in _IO_CODES and ts is not None and t != ts:
+                raise TypeError(f"{name}: typestr {t!r}, expected {ts!r} (one element type per call)")
+            if t in _IO_CODES and ts is None:
+                ts = t
+        return ts or _IO_NAMES[self.dtype]
+
+    def _new(self, shape, typestr):
+        import torch        # lazily: the package does not need torch until an output is omitted
+        dt = {"<f8": torch.float64, "<f4": torch.float32, "<i4": torch.int32, "<i8": torch.int64}[typestr]
+        return torch.empty(shape, dtype=dt, device=f"cuda:{self.device}")
+
+    def set_state_device(self, qpos, qvel, mask=None):
+        """set_state() from device arrays qpos (E, M, 7), qvel (E, M, 6) of one
+        element type.  mask (E,) bool or uint8 on the device: only the
+        environments where it is set are written and reset (None: all); the
+        rows of the others are not read."""
+        E, M = self.n_envs, self.n_bodies
+        ts = self._pair_typestr(("qpos", "qvel"), (qpos, qvel), None)
+        q, _ = _device_array("qpos", qpos, (E, M, 7), (ts,))
+        v, _ = _device_array("qvel", qvel, (E, M, 6), (ts,))
+        m = None if mask is None else _device_array("mask", mask, (E,), ("|b1", "|u1"))[0]
+        _lib.check(self._L.rb_batch_set_state_dev(self._h, m, q, v, _IO_CODES[ts]), "rb_batch_set_state_dev")
+
+    def get_state_device(self, out_qpos=None, out_qvel=None, dtype=None):
+        """(qpos (E, M, 7), qvel (E, M, 6)) of all environments, written into
+        out_qpos / out_qvel, or into new torch tensors of `dtype` ("f64" /
+        "f32"; None: the batch's), valid on the batch's stream."""
+        E, M = self.n_envs, self.n_bodies
+        ts = self._pair_typestr(("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
+        q = self._new((E, M, 7), ts) if out_qpos is None else out_qpos
+        v = self._new((E, M, 6), ts) if out_qvel is None else out_qvel
+        qp, _ = _device_array("out_qpos", q, (E, M, 7), (ts,), out=True)
+        vp, _ = _device_array("out_qvel", v, (E, M, 6), (ts,), out=True)
+        _lib.check(self._L.rb_batch_get_state_dev(self._h, qp, vp, _IO_CODES[ts]), "rb_batch_get_state_dev")
+        return q, v
+
+    def set_xfrc_device(self, xfrc):
+        """set_xfrc() from a device array (E, M, 6).  A non-finite value is
+        found on the device: the upload then writes nothing and the next
+        sync() raises; the batch counts as having forces set either way
+        (set_xfrc(None) clears them).  Not under "balls"."""
+        ts = self._pair_typestr(("xfrc",), (xfrc,), None)
+        x, _ = _device_array("xfrc", xfrc, (self.n_envs, self.n_bodies, 6), (ts,))
+        _lib.check(self._L.rb_batch_set_xfrc_dev(self._h, x, _IO_CODES[ts]), "rb_batch_set_xfrc_dev")
+
+    def status_device(self, out_code=None, out_steps=None):
+        """status() into device arrays: (code (E,) int32, steps_done (E,) int64)."""
+        E = self.n_envs
+        code = self._new((E,), "<i4") if out_code is None else out_code
+        done = self._new((E,), "<i8") if out_steps is None else out_steps
+        cp, _ = _device_array("out_code", code, (E,), ("<i4",), out=True)
+        dp, _ = _device_array("out_steps", done, (E,), ("<i8",), out=True)
+        _lib.check(self._L.rb_batch_status_dev(self._h, cp, dp), "rb_batch_status_dev")
+        return code, done
+
+    def run_sampled_device(self, nsteps: int, every: int, velocities: bool = True, out_qpos=None, out_qvel=None,
+                           dtype=None, dt=None, restitution=None, friction=None, threshold=None):
+        """run_sampled() with the samples in device memory: returns (qpos
+        (S, E, M, 7), qvel (S, E, M, 6) or None), written into out_qpos /
+        out_qvel or new torch tensors of `dtype`, without waiting (sync()
+        reports the failed environments)."""
+        p = self._params(dt, restitution, friction, threshold)
+        nsteps, every = int(nsteps), int(every)
+        S = nsteps // every if every >= 1 and nsteps >= 0 else 0
+        E, M = self.n_envs, self.n_bodies
+        if not velocities and out_qvel is not None:
+            raise ValueError("out_qvel: given with velocities=False")
+        ts = self._pair_typestr(("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
+        q = self._new((S, E, M, 7), ts) if out_qpos is None else out_qpos
+        v = None if not velocities else self._new((S, E, M, 6), ts) if out_qvel is None else out_qvel
+        qp, _ = _device_array("out_qpos", q, (S, E, M, 7), (ts,), out=True)
+        vp = None if v is None else _device_array("out_qvel", v, (S, E, M, 6), (ts,), out=True)[0]
+        if S > 0 and v is not None and vp is None:
+            raise ValueError("out_qvel: null device pointer")
+        _lib.check(self._L.rb_batch_run_sampled_dev(self._h, nsteps, every, *p, qp, vp, _IO_CODES[ts]),
+                   "rb_batch_run_sampled_dev")
+        return q, v

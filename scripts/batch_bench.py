@@ -38,6 +38,19 @@ LAYERS) (columns of cubes, some capped with a sphere: box-involved pairs, the
 mixed-template kernel) with a friction sweep (0.2 .. 0.8 over the
 environments) against one World(scene, max_partners=32).
 
+--device-loop K: instead, a closed loop's iteration (new applied forces, K
+steps, read the state, reset 1 % of the environments) through the
+device-resident boundary (set_xfrc_device, step_async(K), get_state_device,
+set_state_device(mask); torch tensors on the batch's stream, one sync() at the
+end of the timed window) against the same iteration through host arrays
+(set_xfrc, step(K), get_state, set_state(envs=...)) on the same batch,
+alternating; `--steps` iterations per window, seconds per iteration.
+
+--sampled-device EVERY: run_sampled_device(steps, EVERY) into tensors
+allocated once, with its sync(), against run_sampled(steps, EVERY) on the
+same batch, alternating; seconds per run, and the ratio to the same steps
+unsampled.
+
 Prints one JSON line and writes it to --out (default
 profiles/batch/batch_bench.json).  Needs the GPU: there is no fallback.
 """
@@ -201,6 +214,116 @@ def bench_sampled(rb, sc, E, steps, every, reps, dtype, law="mujoco"):
     return out
 
 
+def _words(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def bench_device_loop(rb, sc, E, K, iters, reps, dtype):
+    """Seconds per iteration of the closed loop through device tensors and
+    through host arrays, alternating, from the same start state; the final
+    states must agree word for word in every repeat."""
+    import torch
+    rng = np.random.default_rng(0)
+    q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
+    v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
+    xf = np.concatenate([rng.normal(0.0, 0.5, (E, sc.n, 3)), rng.normal(0.0, 0.05, (E, sc.n, 3))], axis=2)
+    mask = np.zeros(E, bool)
+    mask[::100] = True                                  # 1 % of the environments are reset every iteration
+    ids = np.nonzero(mask)[0]
+    rq, rv = q[ids].copy(), v[ids].copy()
+    with rb.BatchWorld(sc, E, dtype=dtype) as b:
+        b.set_params(restitution=np.linspace(0.5, 1.0, E))
+        b.use_stream(torch.cuda.current_stream().cuda_stream)
+        dev = f"cuda:{b.device}"
+        xf_d, q_d, v_d, mask_d = (torch.from_numpy(a).to(dev) for a in (xf, q, v, mask))
+        out_q, out_v = torch.empty_like(q_d), torch.empty_like(v_d)
+
+        def device_loop(n):
+            for _ in range(n):
+                b.set_xfrc_device(xf_d)
+                b.step_async(K)
+                b.get_state_device(out_q, out_v)
+                b.set_state_device(q_d, v_d, mask=mask_d)
+            if b.sync():
+                raise RuntimeError("environments failed")
+
+        def host_loop(n):
+            for _ in range(n):
+                b.set_xfrc(xf)
+                if b.step(K):
+                    raise RuntimeError("environments failed")
+                b.get_state()
+                b.set_state(rq, rv, envs=ids)
+
+        b.set_state(q, v)
+        device_loop(3)                                  # warm-up of both
+        host_loop(3)
+        t_dev, t_host, same = [], [], True
+        for _ in range(reps):
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            device_loop(iters)
+            t_dev.append((time.perf_counter() - t0) / iters)
+            dq, dv = b.get_state()
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            host_loop(iters)
+            t_host.append((time.perf_counter() - t0) / iters)
+            hq, hv = b.get_state()
+            same = same and bool(np.array_equal(_words(dq), _words(hq)) and np.array_equal(_words(dv), _words(hv)))
+    out = dict(iterations=iters, identical=same, device_s=_summary(t_dev), host_s=_summary(t_host))
+    out["speedup_median"] = out["host_s"]["median"] / out["device_s"]["median"]
+    out["slowest_device_beats_fastest_host"] = out["device_s"]["max"] < out["host_s"]["min"]
+    return out
+
+
+def bench_sampled_device(rb, sc, E, steps, every, reps, dtype):
+    """Seconds per run of run_sampled_device(steps, every) + sync() and of
+    run_sampled(steps, every), alternating, from the same start state; the two
+    must return the same words."""
+    import torch
+    q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
+    v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
+    S = steps // every
+    with rb.BatchWorld(sc, E, dtype=dtype) as b:
+        b.set_params(restitution=np.linspace(0.5, 1.0, E))
+        b.use_stream(torch.cuda.current_stream().cuda_stream)
+        dev = f"cuda:{b.device}"
+        out_q = torch.empty((S, E, sc.n, 7), dtype=torch.float64, device=dev)
+        out_v = torch.empty((S, E, sc.n, 6), dtype=torch.float64, device=dev)
+        b.set_state(q, v)
+        hq, hv, _ = b.run_sampled(steps, every)         # warm-up of both, and the comparison
+        b.set_state(q, v)
+        b.run_sampled_device(steps, every, out_qpos=out_q, out_qvel=out_v)
+        b.sync()
+        same = bool(np.array_equal(_words(out_q.cpu().numpy()), _words(hq)) and
+                    np.array_equal(_words(out_v.cpu().numpy()), _words(hv)))
+        del hq, hv
+        t_dev, t_host, t_plain = [], [], []
+        for _ in range(reps):
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            b.run_sampled_device(steps, every, out_qpos=out_q, out_qvel=out_v)
+            b.sync()
+            t_dev.append(time.perf_counter() - t0)
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            b.run_sampled(steps, every)
+            t_host.append(time.perf_counter() - t0)
+            b.set_state(q, v)
+            t0 = time.perf_counter()
+            b.step(steps)
+            t_plain.append(time.perf_counter() - t0)
+    nbytes = S * E * sc.n * 13 * 8
+    out = dict(samples=S, bytes=nbytes, identical=same, device_s=_summary(t_dev), host_s=_summary(t_host),
+               step_only_s=_summary(t_plain))
+    out["device_bytes_per_s"] = nbytes / out["device_s"]["median"] if S else 0.0
+    out["speedup_median"] = out["host_s"]["median"] / out["device_s"]["median"]
+    out["device_over_step_only"] = out["device_s"]["median"] / out["step_only_s"]["median"]
+    out["slowest_device_beats_fastest_host"] = out["device_s"]["max"] < out["host_s"]["min"]
+    return out
+
+
 def bench_world(rb, sc, steps, reps, dtype, law="mujoco", **kw):
     with (rb.World(sc, dtype=dtype, **kw) if law == "mujoco" else rb.World(sc, dtype=dtype, law=law)) as w:
         w.step(steps)                                   # warm-up (captures the step graph)
@@ -229,6 +352,10 @@ def main():
                     help="N cube-incline angles as one batch against N one-environment batches")
     ap.add_argument("--box-pile", default="", metavar="NX,NY,LAYERS",
                     help="scene box_pile(NX, NY, LAYERS), a friction sweep, against one World(max_partners=32)")
+    ap.add_argument("--device-loop", type=int, default=0, metavar="K",
+                    help="a closed loop's iteration of K steps through device tensors against host arrays")
+    ap.add_argument("--sampled-device", type=int, default=0, metavar="EVERY",
+                    help="time run_sampled_device(steps, EVERY) against run_sampled(steps, EVERY)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "batch_bench.json"))
     a = ap.parse_args()
 
@@ -253,6 +380,17 @@ def main():
         w = res["world"]["median"]
         res["ratio_vs_world"] = {E: dict(median=r["median"] / w, min=r["min"] / w, max=r["max"] / w)
                                  for E, r in res["batch"].items()}
+    elif a.device_loop or a.sampled_device:
+        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep:
+            raise SystemExit("--device-loop / --sampled-device: on their own, under the default law")
+        if a.device_loop:
+            res.update(unit="seconds per iteration", steps_per_iteration=a.device_loop, iterations=a.steps)
+            res["device_loop"] = {str(E): bench_device_loop(rbhip, sc, E, a.device_loop, a.steps, a.reps, a.dtype)
+                                  for E in a.envs}
+        else:
+            res.update(unit="seconds per run", every=a.sampled_device)
+            res["sampled_device"] = {str(E): bench_sampled_device(rbhip, sc, E, a.steps, a.sampled_device, a.reps, a.dtype)
+                                     for E in a.envs}
     elif a.incline_sweep:
         res.update(scene="cube_incline", bodies_per_env=1, dtype="f64", unit="seconds per run")
         res["incline_sweep"] = bench_incline_sweep(rbhip, a.incline_sweep, a.steps, a.reps)
