@@ -90,8 +90,8 @@ template <typename T> StepParams<T> make_step(rb_world *w, int64_t c, double dt,
     }
     if (insert_next && epoch_eligible(w)) {
         int32_t *crowd = reinterpret_cast<int32_t *>(w->ep_mem + 2);
-        p.ep.ctrl = w->ep_mem + sp;
-        p.ep.ctrl_next = w->ep_mem + (1 - sp);
+        p.ep.ctrl = w->ep_ctrl() + sp;
+        p.ep.ctrl_next = w->ep_ctrl() + (1 - sp);
         for (int k = 0; k < 2; ++k) { p.ep.line[k] = w->ids[k]; p.ep.spill[k] = w->spill[k]; }
         p.ep.crowd = crowd + sp;
         p.ep.crowd_prev = crowd + (1 - sp);
@@ -148,7 +148,7 @@ int prime(rb_world *w, double dt, double e, double mu) {
     w->ep_primed = epoch_eligible(w);
     if (w->ep_primed) {
         const uint32_t cw = epoch_word((uint32_t)w->sp(), 0u, std::min((uint32_t)w->epoch_max, EP_START_LEN), false, 0u);
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w->ep_mem + w->sp()), (int)cw, 1, w->stream));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w->ep_ctrl() + w->sp()), (int)cw, 1, w->stream));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w->ep_mem + 2), 0, 2, w->stream));
     }
     w->primed = true;

@@ -88,7 +88,7 @@ void free_world(rb_world *w) {
     if (w->io_v_d) (void)hipFree(w->io_v_d);
     for (hipEvent_t &e : w->io_ev)
         if (e) (void)hipEventDestroy(e);
-    void *bufs[] = {w->snap[0], w->snap[1], w->qsnap[0], w->qsnap[1], w->defer_q, w->defer_cnt, w->state, w->consts, w->kind, w->xfrc, w->gen, w->ep_mem,
+    void *bufs[] = {w->snap[0], w->snap[1], w->qsnap[0], w->qsnap[1], w->defer_q, w->defer_cnt, w->state, w->consts, w->kind, w->xfrc, w->lead_blk, w->ep_mem,
                     w->ids[0], w->ids[1], w->spill[0], w->spill[1], w->pos[0], w->pos[1], w->plist, w->plist_cnt, w->vel[0], w->vel[1], w->err, w->rec_count, w->rec_partner, w->rec_kind,
                     w->rec_dist};
     for (void *b : bufs)
@@ -281,7 +281,8 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     ALLOC(w->state, (size_t)w->esz * 13 * w->S);
     ALLOC(w->consts, (size_t)w->esz * 8 * w->Npad);
     ALLOC(w->kind, sizeof(int32_t) * w->Npad);
-    ALLOC(w->gen, sizeof(uint32_t) * 2);
+    ALLOC(w->lead_blk, sizeof(uint32_t) * LEAD_WORDS);   // (hipMalloc: aligned to 16 bytes and more)
+    w->gen = w->lead_blk + LEAD_GEN;
     ALLOC(w->ep_mem, sizeof(uint32_t) * 8);
     // Opt-in (RBHIP_SPLIT=1): large scenes step in two kernels (search,
     // update) joined by a partner list; bit-exact with the oracle on the
@@ -318,7 +319,7 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
             {w->ids[0], sizeof(uint32_t) * LINE_WORDS * w->H}, {w->ids[1], sizeof(uint32_t) * LINE_WORDS * w->H},
             {w->spill[0], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES},
             {w->spill[1], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES},
-            {w->gen, sizeof(uint32_t) * 2}, {w->ep_mem, sizeof(uint32_t) * 8}, {w->err, sizeof(int32_t)}, {w->defer_cnt, sizeof(int32_t) * 2}};
+            {w->lead_blk, sizeof(uint32_t) * LEAD_WORDS}, {w->ep_mem, sizeof(uint32_t) * 8}, {w->err, sizeof(int32_t)}, {w->defer_cnt, sizeof(int32_t) * 2}};
         for (const auto &z : zero)
             if (z.first && hipMemsetAsync(z.first, 0, z.second, w->stream) != hipSuccess)
                 return bail(fail(RB_ENODEV, "hipMemsetAsync failed"));

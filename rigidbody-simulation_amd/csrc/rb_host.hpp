@@ -100,14 +100,19 @@ struct rb_world {
     uint32_t *ids[2] = {};     // [H][LINE_WORDS] bucket blocks (rb_internal.hpp Table; alternate with the snapshots)
     uint32_t *spill[2] = {};   // [SPILL_LINES x SPILL_LINE_WORDS] ids past full buckets, per table
     void *pos[2] = {};         // [H][LINE_WORDS] Snap<T> bucket slot snapshots
-    uint32_t *gen = nullptr;   // [2] generation of the table of each step parity (rb_internal.hpp Table)
+    // the step kernels' lead block (rb_internal.hpp LEAD_WORDS), one allocation:
+    // generations [2] and epoch control words [2] by step parity.  prime()
+    // writes the current parity's words; the step kernels' block 0 the other's
+    uint32_t *lead_blk = nullptr;
+    uint32_t *gen = nullptr;   // [2] generation of the table of each step parity (rb_internal.hpp Table): lead_blk + LEAD_GEN
     uint32_t gen_off = 1;      // an upper bound of step c's generation: gen_off + c (host bookkeeping; only
                                // grows; append steps keep their table's generation, so the device's lag it)
-    // append epochs (rb_internal.hpp Epoch): one allocation — control words
-    // [2] by step parity, crowding flags [2], counters [2] (append steps,
-    // rebuild steps)
+    // append epochs (rb_internal.hpp Epoch): the control words [2] by step
+    // parity are lead_blk + LEAD_CTRL; ep_mem, one allocation — two unused
+    // words, crowding flags [2], counters [2] (append steps, rebuild steps)
     int32_t epoch_max = EPOCH_DEFAULT;   // RBHIP_TABLE_EPOCH; 1: every step rebuilds its next table
     uint32_t *ep_mem = nullptr;
+    uint32_t *ep_ctrl() const { return lead_blk + LEAD_CTRL; }
     bool ep_primed = false;        // the last prime() started an epoch schedule
     int32_t *plist = nullptr;      // split form: [MAXP][S] sorted partner ids
     int32_t *plist_cnt = nullptr;  // split form: [S] partner counts

@@ -54,6 +54,16 @@ constexpr int LINE_WORDS = 32;               // uint32 words per bucket (head + 
 constexpr int HEAD_WORDS = 2;                // the header's words
 constexpr int BUCKET_SLOTS = LINE_WORDS - HEAD_WORDS;
 constexpr uint32_t BOX_FLAG = 0x80000000u;   // set on ids of box bodies
+// The words a step kernel's lead needs, in one 16-byte-aligned device
+// allocation (rb_host.hpp lead_blk): {gen[0], gen[1], ctrl[0], ctrl[1]} — the
+// generation of the table of each step parity and the append epochs' control
+// word of each step parity (Epoch; unused in worlds without epochs).
+// Table::gen, Epoch::ctrl and Epoch::ctrl_next point into it.  The step
+// kernels of worlds with append epochs read the whole block with one scalar
+// load as they start (rb_step.hpp lead_words); every other kernel reads its
+// word through those pointers.  The step of parity sp reads gen[sp] and
+// ctrl[sp], and its block 0 writes gen[1 - sp] and ctrl[1 - sp].
+constexpr int LEAD_GEN = 0, LEAD_CTRL = 2, LEAD_WORDS = 4;
 template <typename T> struct Table {
     uint32_t *line;            // [H / R][R x LINE_WORDS] bucket blocks: heads, then further ids
     Snap<T> *pos;              // [H][LINE_WORDS] slot snapshots (slot s at s); nullptr: not kept
@@ -218,7 +228,8 @@ __host__ __device__ inline uint32_t epoch_word(uint32_t tab, uint32_t age, uint3
            (len << EP_LEN_SHIFT) | (start << EP_START_SHIFT);
 }
 struct Epoch {
-    const uint32_t *ctrl;              // this step's control word; nullptr: no epochs (cur / next as given)
+    const uint32_t *ctrl;              // this step's control word (in the lead block); nullptr: no epochs
+                                       // (cur / next as given)
     uint32_t *ctrl_next;               // the next step's
     uint32_t *line[2], *spill[2];      // both tables
     int32_t *crowd, *crowd_prev;       // crowding flag raised by this step's claims / by the step before

@@ -284,14 +284,52 @@ template <typename T> __device__ __forceinline__ BodyIn<T> load_body(const StepP
 // -amdgpu-kernarg-preload-count), so their first loads wait for no scalar
 // load of the parameter block (measured 0.27 us per launch in
 // scripts/preload_probe.hip); the box kernel takes them from the block.
+// 14 dwords: the preload budget beside the two of the kernarg pointer.
+//
+// The instances of worlds with append epochs (the _ep kernels of
+// rb_step_wide.hip) take LEAD_EP_*: the address of the lead block's
+// generation word as well (gen_cur, lead_words below), for which the row
+// strides (st.S, cs.Npad) travel as 32-bit values — they count bodies, as
+// n_local and lo do; cs.kind stays a pointer (an allocation of its own, at no
+// fixed distance from cs.base).  Every other instance keeps LEAD_* and reads
+// its generation through the parameter block (body_step): there the early
+// read lost (C2, cooperative form: 6.98 -> 7.13 us per step; C5: 8.72 -> 9.18)
 template <typename T> struct Lead {
     const Snap<T> *snap_cur;
     BodyState<T> st;
     BodyConsts<T> cs;
     int32_t n_local, lo;
+    const uint32_t *gen_cur = nullptr; // _ep kernels: p.cur.gen, gen[step parity] of the lead block (rb_internal.hpp)
     __device__ static Lead of(const StepParams<T> &p) { return Lead{p.snap_cur, p.st, p.cs, p.n_local, p.lo}; }
 };
 #define LEAD_ARGS(p) (p).snap_cur, (p).st.base, (p).st.S, (p).cs.base, (p).cs.Npad, (p).cs.kind, (p).n_local, (p).lo
+#define LEAD_EP_PARAMS(T)                                                                                         \
+    const Snap<T> *snap_cur, T *st_base, const T *cs_base, const int32_t *cs_kind, const uint32_t *gen_cur,       \
+        int32_t st_S, int32_t cs_Npad, int32_t n_local, int32_t lo
+#define LEAD_EP_OF(T)                                                                                             \
+    Lead<T> { snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo, gen_cur }
+#define LEAD_EP_ARGS(p)                                                                                           \
+    (p).snap_cur, (p).st.base, (p).cs.base, (p).cs.kind, (p).cur.gen, (int32_t)(p).st.S, (int32_t)(p).cs.Npad, (p).n_local, (p).lo
+
+// The lead block's words of this step: its table's generation and its epoch
+// control word, with ONE scalar load of the block, issued from preloaded
+// SGPRs — beside the parameter block's scalar loads, not behind them, and
+// behind no vector load.  gen_cur points at gen[sp] inside the 16-byte-aligned
+// block, so the block's address and the step's parity sp both come from it.
+// Why a scalar (constant address space) read is sound: the step of parity sp
+// reads only gen[sp] and ctrl[sp], and no thread of the same launch writes
+// those — block 0 writes gen[1 - sp] and ctrl[1 - sp] (step_body's tail),
+// words this step never looks at; every writer between launches (prime(),
+// the step before) is ordered before this launch on the stream.
+struct LeadWords { uint32_t gen, ctrl; };
+typedef uint32_t lead_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ LeadWords lead_words(const uint32_t *gen_cur) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(gen_cur);
+    const lead_u32x4 b = *(const __attribute__((address_space(4))) lead_u32x4 *)(a & ~uintptr_t(4 * LEAD_WORDS - 1));
+    const bool odd = (a & 4u) != 0;
+    static_assert(LEAD_GEN == 0 && LEAD_CTRL == 2 && LEAD_WORDS == 4, "the block's layout");
+    return LeadWords{odd ? b.y : b.x, odd ? b.w : b.z};
+}
 
 #ifndef RB_SOLVE_PIPE
 #define RB_SOLVE_PIPE 1
@@ -546,7 +584,8 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
                                           int32_t *s_id, Snap<T> *s_pos, int32_t *t_id, Snap<T> *t_pos,
                                           uint32_t *s_cand, int32_t *cell, uint32_t gen, T *s_poly,
                                           uint8_t *s_didx = nullptr, Snap<T> *s_hpos = nullptr,
-                                          T *s_help = nullptr, int role = 0, uint32_t *s_half = nullptr) {
+                                          T *s_help = nullptr, int role = 0, uint32_t *s_half = nullptr,
+                                          uint32_t ctrl = 0u /* PRE && EP: the step's epoch control word */) {
     static_assert(!SHARE || (G == 1 && WIDE && HELP && !BOXES), "shared search: the helper-wave wide form");
     constexpr int NB = STEP_BLOCK / G;
     const int32_t l = active ? (int32_t)lb : 0;
@@ -556,12 +595,25 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     const Snap<T> self = xld(ld.snap_cur + i);
     const V3<T> x = {self.x, self.y, self.z};
     const int32_t ci = RB_ABLATE == 8 ? 0 : i;    // (diagnostic, load_body)
-    const int32_t kind = ld.cs.kind[ci];
+    // worlds with epochs, shared search: the kind-dependent selects below are
+    // made under the head loads (late_kind, called by the search's overlap):
+    // the wait for kind, sy and sz counts loads in issue order, so ahead of
+    // the heads it would hold them back until the finishing wave's state
+    // loads, issued after these, had landed
+    constexpr bool LATE = SHARE && EP;
+    int32_t kind = ld.cs.kind[ci];
     const T bi = self.r;
     // half extents y, z only matter for boxes; loaded for every body (a load
     // under a kind test would wait for kind before the state loads issue)
-    const T sy = ld.cs.sy()[ci], szz = ld.cs.sz()[ci];
-    const V3<T> sz = {ld.cs.sx()[ci], kind != 0 ? sy : T(0), kind != 0 ? szz : T(0)};
+    T sy = ld.cs.sy()[ci], szz = ld.cs.sz()[ci];
+    V3<T> sz = {ld.cs.sx()[ci], !LATE && kind != 0 ? sy : T(0), !LATE && kind != 0 ? szz : T(0)};
+    [[maybe_unused]] auto late_kind = [&] {
+        if constexpr (LATE) {
+            asm volatile("" : "+v"(kind), "+v"(sy), "+v"(szz));
+            sz.y = kind != 0 ? sy : T(0);
+            sz.z = kind != 0 ? szz : T(0);
+        }
+    };
     BodyIn<T> in;
     LazyInvI<T> invI;
     bool forced = false;
@@ -589,15 +641,26 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     }
     if constexpr (PRE) {
         // preloaded lead (step_body): the parameter block's fields the search
-        // starts with, in one scalar round trip under the body's loads (which
-        // needed none of them)
-        asm volatile("" ::"s"(p.grid.inv_cs), "s"(p.grid.H), "s"(p.grid.super), "s"(p.cur.line), "s"(p.cur.gen),
-                     "s"(p.n_global), "s"(p.xfrc));
-        if constexpr (G > 1) asm volatile("" ::"s"(p.cur.pos));
-        // (the epoch fields too: the bucket head loads wait for the table's
-        // choice, so they belong to the same scalar round trip)
-        if constexpr (EP) asm volatile("" ::"s"(p.ep.ctrl), "s"(p.ep.line[0]), "s"(p.ep.line[1]));
-        gen = *p.cur.gen;
+        // starts with — every one the bucket head addresses need — in one
+        // scalar round trip under the body's loads (which needed none of
+        // them).  One statement: each such statement waits for its operands
+        if constexpr (EP) {
+            // (the lead block's words too: the table's choice comes before
+            // the head addresses; step_body issued their load first)
+            asm volatile("" ::"s"(gen), "s"(ctrl), "s"(p.grid.inv_cs), "s"(p.grid.H), "s"(p.grid.super),
+                         "s"(p.cur.line), "s"(p.n_global), "s"(p.xfrc), "s"(p.ep.line[0]), "s"(p.ep.line[1]),
+                         "s"(p.ep.spill[0]), "s"(p.ep.spill[1]));
+        } else {
+            asm volatile("" ::"s"(p.grid.inv_cs), "s"(p.grid.H), "s"(p.grid.super), "s"(p.cur.line), "s"(p.cur.gen),
+                         "s"(p.n_global), "s"(p.xfrc));
+            if constexpr (G > 1) asm volatile("" ::"s"(p.cur.pos));
+            // worlds without epochs need the generation only once the heads
+            // are back: its load goes out here, ahead of theirs, and waits
+            // with them.  (The scalar read of the lead block ahead of the
+            // parameter block measured C2 6.98 -> 7.13 us per step in the
+            // cooperative form: every scalar wait then also waits for it)
+            gen = *p.cur.gen;
+        }
     }
     // append epochs (EP: launches of worlds that run them, launch_step_wide;
     // rb_internal.hpp Epoch): the control word picks the table this step
@@ -613,7 +676,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     if constexpr (EP) {
         static_assert(PRE && WIDE, "append epochs: the wide step kernels");
         {
-            const uint32_t cw = *p.ep.ctrl;
+            const uint32_t cw = ctrl;                // (== *p.ep.ctrl: the lead block's word of this parity)
             const uint32_t t = cw & EP_TAB;
             ep_append = (cw & EP_APPEND) != 0;
             ep_appended = ep_append || ((cw >> EP_AGE_SHIFT) & 255u) != 0;
@@ -661,6 +724,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
                 p, i, x, role, s_id, s_cand, s_hpos, tid, gen, cur, b0,
                 [&](uint32_t tj, const Snap<T> &s) { return candidate_hit<T, BOXES>(p, i, kind, x, sz.x, bi, tj, s, defer); },
                 [&] {
+                    if constexpr (LATE) late_kind();
                     if (!role) return;
                     hm = invI.get();
                     if (!work2) own_planes();
@@ -670,6 +734,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
                     __builtin_amdgcn_sched_barrier(0);   // the candidate loads issue before the work
                     own_planes();
                 });
+        else if constexpr (LATE) late_kind();    // (no search: idle lanes, a diagnostic build)
         // the wave that does not finish leaves its hit count and defer flag
         if ((FIN ? !role : role) && active)
             s_half[tid] = (uint32_t)(n_half < 0xffff ? n_half : 0xffff) | (defer ? 1u << 16 : 0u);
@@ -949,6 +1014,14 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
         rb_stamp_buf[blockIdx.x][14] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
     }
 #endif
+    // worlds with append epochs: the kernel's first load is the lead block,
+    // from preloaded SGPRs (after the first stamp of a diagnostic build,
+    // which waits for scalar loads); the others: body_step
+    LeadWords lw{0u, 0u};
+    if constexpr (EP) {
+        lw = lead_words(ld.gen_cur);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // The lead (the body's first loads' fields) is preloaded; body_step waits
     // for the parameter block's scalar loads only under the body's loads.
     // Block 0 advances the exchange's step number and publishes the next
@@ -963,8 +1036,8 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     int32_t cell[6] = {INT32_MAX, 0, 0, 0, 0, 0};   // new cell, step-start cell (peer-to-peer exchange)
     if (G > 1 || HELP || active)                 // (a helper's barriers: every lane)
         body_step<T, MAXP, G, WIDE, BOXES, true, HELP, EP, SHARE>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos,
-                                                              s_cand, cell, 0u /* loaded in body_step */, s_poly, s_didx,
-                                                              s_hpos, help_lds, role, s_half);
+                                                              s_cand, cell, lw.gen, s_poly, s_didx, s_hpos, help_lds, role,
+                                                              s_half, lw.ctrl);
     // shared search: the body wave is done; the helper wave, which finished
     // the bodies, holds their cells and does the rest (its tid 0: block 0's stores)
     // (MAXP 32 instances: the body wave finishes and the helper is done)
