@@ -2,7 +2,9 @@
 // they share with the wide forms: rb_step.hpp): the cooperative form, with
 // and without a helper wave, the one-lane form, the box kernel, the split
 // form's search and update kernels, and launch_step, which picks among them
-// (the wide forms through rb_step_wide.hip's launch_step_wide).
+// (the wide forms through rb_step_wide.hip's launch_step_wide).  Each kernel
+// names its form (rb_step.hpp FormDefaults: Coop, CoopHelp, One, BoxBody,
+// SplitUpdate); the launcher turns maxp into a constant with pick().
 // Built once per real type: RB_INST = 1 fp64, 2 fp32.
 
 // the phase stamps are the wide unit's (rb_step_wide.hip)
@@ -26,30 +28,24 @@ namespace rb {
 template <typename T, int MAXP>
 __global__ __launch_bounds__(STEP_BLOCK)
 __attribute__((amdgpu_waves_per_eu(MAXP <= 16 ? RB_MIN_WAVES_COOP : 2)))   // 32 partners: 2 fit
-void step_kernel_coop(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                      const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 8, false, false>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
+void step_kernel_coop(LEAD_PARAMS(T), StepParams<T> p) {
+    step_body<T, Coop<MAXP>>(p, LEAD_OF(T));
 }
 // the cooperative form with a helper wave per workgroup (help_body): small
 // scenes, whose body waves leave SIMDs idle
 template <typename T, int MAXP>
 __global__ __launch_bounds__(2 * STEP_BLOCK)
 __attribute__((amdgpu_waves_per_eu(MAXP <= 16 ? RB_MIN_WAVES_COOP : 2)))
-void step_kernel_coop_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                           const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 8, false, false, true>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
+void step_kernel_coop_help(LEAD_PARAMS(T), StepParams<T> p) {
+    step_body<T, CoopHelp<MAXP>>(p, LEAD_OF(T));
 }
 template <typename T, int MAXP>
 __global__ __launch_bounds__(STEP_BLOCK)
 #if RB_MIN_WAVES_G1 > 1
 __attribute__((amdgpu_waves_per_eu(RB_MIN_WAVES_G1)))
 #endif
-void step_kernel_one(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                     const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, false, false>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
+void step_kernel_one(LEAD_PARAMS(T), StepParams<T> p) {
+    step_body<T, One<MAXP>>(p, LEAD_OF(T));
 }
 // The box kernel (box worlds, after the step kernel): steps the bodies the
 // step kernel deferred — those with a box-involved partner within bounding
@@ -77,8 +73,10 @@ void box_kernel(StepParams<T> p) {
         // one lane per body: the lane's LDS column (partner list, polygon) is slot = tid
         if (qi < n) {
             l = p.defer_q[qi];
-            body_step<T, MAXP, 1, false, true>(p, Lead<T>::of(p), true, l, tid, 0, tid, s_id, nullptr, nullptr, nullptr,
-                                               nullptr, cell, gen, s_poly);
+            // (of body_step's LDS arrays the box kernel has the list and the polygons; no helper, no epochs)
+            body_step<T, BoxBody<MAXP>>(
+                p, Lead<T>::of(p), true, l, tid, 0, tid, s_id, nullptr, nullptr, nullptr, nullptr, cell, gen, s_poly, nullptr,
+                nullptr, nullptr, 0, nullptr, 0u);
         }
         if (halo) halo_push(p, halo_e, cell[0] != INT32_MAX, p.lo + l, cell, hb);   // (every lane of the wave)
         if (cell[0] != INT32_MAX)
@@ -147,8 +145,9 @@ __global__ __launch_bounds__(STEP_BLOCK) void update_kernel(StepParams<T> p) {
         invI.q = in.q;
         const int32_t np_ = p.plist_cnt[CHK(l, p.S)];
         if (RB_BOUNDS && np_ > 16) printf("RB_BOUNDS np_ %d at l %d\n", np_, l);
-        body_update<T, 0>(p, l, i, x, kind, sz, self.r, in, false, invI, Partners<T>{np_, p.plist + l, p.S}, HelpDone{},
-                          NextTable<T>{gen_next}, tid, cell, nullptr, 0);
+        body_update<T, FormTraits<SplitUpdate>::Update>(p, l, i, x, kind, sz, self.r, in, false, invI,
+                                                        Partners<T>{np_, p.plist + l, p.S}, HelpDone{},
+                                                        NextTable<T>{gen_next}, tid, cell, nullptr, 0);
     }
     if (p.bounds) fold_bounds(p.bounds, cell);
     if (p.halo.mail) {                           // halo-exchanging shard: push to the peers
@@ -167,30 +166,27 @@ template <typename T> hipError_t launch_step(const StepParams<T> &p, int maxp, i
     // the cooperative search reads bucket slot snapshots: never launch it
     // on a table without them
     if (needs_slot_snapshots(coop, split) && (!p.cur.pos || (p.next.line && !p.next.pos))) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), one(STEP_BLOCK), two(2 * STEP_BLOCK);
+    const bool m16 = maxp <= 16;
     if (split) {
         constexpr int GS = SPLIT_SEARCH_LANES;
-        const int64_t sblocks = blocks * GS;
-        if (maxp <= 16) hipLaunchKernelGGL((search_kernel<T, 16, GS>), dim3((unsigned)sblocks), dim3(STEP_BLOCK), 0, s, p);
-        else hipLaunchKernelGGL((search_kernel<T, 32, GS>), dim3((unsigned)sblocks), dim3(STEP_BLOCK), 0, s, p);
-        hipLaunchKernelGGL((update_kernel<T>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, p);
-    } else if (coop && form == FORM_COOP_HELP) {   // (box worlds: the box kernel follows)
-        if (maxp <= 16) hipLaunchKernelGGL((step_kernel_coop_help<T, 16>), dim3((unsigned)blocks), dim3(2 * STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-        else hipLaunchKernelGGL((step_kernel_coop_help<T, 32>), dim3((unsigned)blocks), dim3(2 * STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
+        const dim3 sgrid((unsigned)(blocks * GS));
+        pick([&](auto m) { hipLaunchKernelGGL((search_kernel<T, maxp_c(m.value), GS>), sgrid, one, 0, s, p); }, m16);
+        hipLaunchKernelGGL((update_kernel<T>), grid, one, 0, s, p);
+    } else if (form == FORM_COOP_HELP) {         // (box worlds: the box kernel follows)
+        pick([&](auto m) { hipLaunchKernelGGL((step_kernel_coop_help<T, maxp_c(m.value)>), grid, two, 0, s, LEAD_ARGS(p), p); }, m16);
     } else if (coop) {
-        if (maxp <= 16) hipLaunchKernelGGL((step_kernel_coop<T, 16>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-        else hipLaunchKernelGGL((step_kernel_coop<T, 32>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
+        pick([&](auto m) { hipLaunchKernelGGL((step_kernel_coop<T, maxp_c(m.value)>), grid, one, 0, s, LEAD_ARGS(p), p); }, m16);
     } else if (form == FORM_WIDE || form == FORM_WIDE_HELP) {
         const hipError_t we = launch_step_wide<T>(p, maxp, form == FORM_WIDE_HELP, share, s);
         if (we != hipSuccess) return we;
     } else {
-        if (maxp <= 16) hipLaunchKernelGGL((step_kernel_one<T, 16>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
-        else hipLaunchKernelGGL((step_kernel_one<T, 32>), dim3((unsigned)blocks), dim3(STEP_BLOCK), 0, s, LEAD_ARGS(p), p);
+        pick([&](auto m) { hipLaunchKernelGGL((step_kernel_one<T, maxp_c(m.value)>), grid, one, 0, s, LEAD_ARGS(p), p); }, m16);
     }
     if (boxes) {
         const int64_t bb = (p.n_local + STEP_BLOCK - 1) / STEP_BLOCK;
-        const unsigned nbb = (unsigned)(bb < 1 ? 1 : bb > 256 ? 256 : bb);
-        if (maxp <= 16) hipLaunchKernelGGL((box_kernel<T, 16>), dim3(nbb), dim3(STEP_BLOCK), 0, s, p);
-        else hipLaunchKernelGGL((box_kernel<T, 32>), dim3(nbb), dim3(STEP_BLOCK), 0, s, p);
+        const dim3 bgrid((unsigned)(bb < 1 ? 1 : bb > 256 ? 256 : bb));
+        pick([&](auto m) { hipLaunchKernelGGL((box_kernel<T, maxp_c(m.value)>), bgrid, one, 0, s, p); }, m16);
     }
     return hipGetLastError();
 }

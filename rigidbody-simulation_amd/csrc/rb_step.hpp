@@ -25,6 +25,8 @@
 //   multi_sphere_bounce.py:43-46 (one mj_forward per step).
 #pragma once
 
+#include <type_traits>
+
 #include "rb_device.hpp"
 
 // diagnostic build only: per-wave s_memtime stamps at phase boundaries, into
@@ -302,6 +304,11 @@ template <typename T> struct Lead {
     const uint32_t *gen_cur = nullptr; // _ep kernels: p.cur.gen, gen[step parity] of the lead block (rb_internal.hpp)
     __device__ static Lead of(const StepParams<T> &p) { return Lead{p.snap_cur, p.st, p.cs, p.n_local, p.lo}; }
 };
+#define LEAD_PARAMS(T)                                                                                            \
+    const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad, const int32_t *cs_kind, \
+        int32_t n_local, int32_t lo
+#define LEAD_OF(T)                                                                                                \
+    Lead<T> { snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo }
 #define LEAD_ARGS(p) (p).snap_cur, (p).st.base, (p).st.S, (p).cs.base, (p).cs.Npad, (p).cs.kind, (p).n_local, (p).lo
 #define LEAD_EP_PARAMS(T)                                                                                         \
     const Snap<T> *snap_cur, T *st_base, const T *cs_base, const int32_t *cs_kind, const uint32_t *gen_cur,       \
@@ -361,6 +368,89 @@ template <int MAXP> constexpr bool share_finish() { return MAXP <= 16 || RB_SHAR
 #define RB_SOLVE_DEPTH 1
 #endif
 
+// ---- a step kernel's form ---------------------------------------------------
+// step_body and body_step take one type F that names the form: a struct of
+// the flags below, every one with a default here.  The forms that exist are
+// the structs after it; a call site names one of them.  A form holds only what
+// body_step depends on (HALO is step_body's own parameter), and body_update
+// takes the smaller UpdateForm: kernels that agree in what a function sees
+// share one instance of it, as they always did — with an instance per kernel
+// the wide unit's instructions come out in another order
+// (profiles/step_forms/README.md).
+struct FormDefaults {
+    static constexpr int G = 1;            // lanes per body: 1, or 8 (the cooperative search, one per neighbour cell)
+    // the one-lane form for one wave per SIMD (search_buckets_wide; state
+    // loads and inv(I_w) under the head loads)
+    static constexpr bool WIDE = false;
+    static constexpr bool BOXES = false;   // the box kernel's body: box-involved pairs and their narrowphase
+    static constexpr bool HELP = false;    // a helper wave per workgroup (help_body)
+    static constexpr bool EP = false;      // worlds with append epochs (the _ep kernels; rb_internal.hpp Epoch)
+    // SHARE: the helper wave of the wide form also searches half of each body's
+    // neighbourhood (body_step; rb_grid.hpp search_half_wide) and then finishes
+    // the body — merge, solves, integration, insert and step_body's tail —
+    // from its own registers; the body wave only searches
+    static constexpr bool SHARE = false;
+    // the lead is preloaded (step_body's callers); false only for the box
+    // kernel's call of body_step, which takes it from the parameter block
+    static constexpr bool PRE = true;
+};
+template <int M> struct One : FormDefaults { static constexpr int MAXP = M; };
+template <int M> struct Coop : One<M> { static constexpr int G = 8; };
+template <int M> struct CoopHelp : Coop<M> { static constexpr bool HELP = true; };
+template <int M> struct Wide : One<M> { static constexpr bool WIDE = true; };
+template <int M, bool S> struct WideHelp : Wide<M> { static constexpr bool HELP = true, SHARE = S; };
+template <int M> struct WideEp : Wide<M> { static constexpr bool EP = true; };
+template <int M, bool S> struct WideHelpEp : WideHelp<M, S> { static constexpr bool EP = true; };
+template <int M> struct BoxBody : One<M> { static constexpr bool BOXES = true, PRE = false; };
+struct SplitUpdate : One<32> {};             // the split form's update_kernel (body_update alone, its list in HBM)
+
+// body_update's form — the partner mode, the box narrowphase, the solve
+// depth, the epochs' crowding flag — and what follows from it
+template <int PM_, bool BOXES_, int SD_, bool EP_> struct UpdateForm {
+    static constexpr int PM = PM_, SD = SD_;
+    static constexpr bool BOXES = BOXES_, EP = EP_;
+    // sphere kernels (RB_SOLVE_PIPE): the next batch's snapshots load under
+    // this batch's solves — a body with many partners (C4's pile-ups: up to
+    // 28) otherwise waits one round trip per batch of partners re-read from memory
+    static constexpr bool PIPE = !BOXES && RB_SOLVE_PIPE && PM != 1;   // (the cooperative form: LDS only)
+    static constexpr bool DEEP = PIPE && SD > 1;
+    // the next table's insert.  The one-lane and wide forms (and the split
+    // form's update) run in linear-layout worlds only; the cooperative form
+    // and the box kernel read the layout
+    static constexpr int L = (PM == 2 || (PM == 0 && !BOXES)) ? LAYOUT_LINEAR : LAYOUT_ANY;
+    // heads per line: known in the cooperative and wide forms (rb_api_world.hip)
+    static constexpr int RL = PM == 1 ? 0 : PM == 2 ? 2 : -1;
+};
+// What follows from a form, and which forms there are.
+template <typename F> struct FormTraits {
+    static_assert(F::G == 1 || F::G == 8, "one lane per body, or one per neighbour cell");
+    static_assert(!F::SHARE || (F::G == 1 && F::WIDE && F::HELP && !F::BOXES), "shared search: the helper-wave wide form");
+    static_assert(!F::EP || (F::PRE && F::WIDE), "append epochs: the wide step kernels");
+    static_assert(!F::HELP || !F::BOXES, "helper waves: the sphere step kernels");
+    static constexpr int NB = STEP_BLOCK / F::G;          // bodies per workgroup
+    // state loads issued before the search (the wide form measured 5 % slower
+    // with them issued after the bucket heads, C3)
+    static constexpr bool EARLY = F::G > 1 || F::WIDE;
+    // worlds with epochs, shared search: the kind-dependent selects of
+    // body_step are made under the head loads (late_kind, called by the
+    // search's overlap): the wait for kind, sy and sz counts loads in issue
+    // order, so ahead of the heads it would hold them back until the
+    // finishing wave's state loads, issued after these, had landed
+    static constexpr bool LATE = F::SHARE && F::EP;
+    // shared search: the helper wave finishes the body (share_finish above)
+    static constexpr bool FIN = F::SHARE && share_finish<F::MAXP>();
+    // shared search, the helper wave's gravity and plane contacts under its
+    // first candidate batch (RB_SHARE_WORK2 above; not with applied forces:
+    // body_update's)
+    static constexpr bool WORK2 = F::MAXP > 16 ? RB_SHARE_WORK2_32 != 0 : RB_SHARE_WORK2 != 0;
+    // body_update's: the partner mode (Partners below) and the batches of
+    // partner snapshots ahead of the solve (RB_SOLVE_DEPTH above)
+    static constexpr int PM = F::G > 1 ? 1 : (F::WIDE && RB_WIDE_LDSPOS) ? 2 : 0;
+    static constexpr int SD = (F::WIDE && F::HELP) ? RB_SOLVE_DEPTH : 1;
+    // what body_update depends on: the forms that agree in it share one instance
+    using Update = UpdateForm<PM, F::BOXES, SD, F::EP>;
+};
+
 // body_update's inputs beside the body itself.
 // The sorted partner list: n ids at id[u * stride] (an LDS column, or the
 // split form's per-slot list in HBM); snapshots (PM, partner mode) at
@@ -395,11 +485,13 @@ template <typename T> struct NextTable {
 // already applied: forced), the Gauss-Seidel solves in canonical order,
 // integration, next-step insert.  poly, ps: the box kernel's clipping
 // polygon column in LDS and its stride (BOXES).
-template <typename T, int PM, bool BOXES = false, int SDEPTH = 1, bool EP = false>
+template <typename T, typename U>
 __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, int32_t i, V3<T> x, int32_t kind,
                                             V3<T> sz, T bi, const BodyIn<T> &in, bool forced, LazyInvI<T> &invI,
                                             const Partners<T> &pa, const HelpDone &help, const NextTable<T> &nx,
                                             int tid, int32_t *cell, T *poly, int ps) {
+    constexpr int PM = U::PM;
+    constexpr bool BOXES = U::BOXES, EP = U::EP;
     const int32_t np_ = pa.n;
     const Q4<T> q = in.q;
     V3<T> v = in.v;
@@ -442,13 +534,10 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
             }
         }
     };
-    // sphere kernels (RB_SOLVE_PIPE): the next batch's snapshots load under
-    // this batch's solves — a body with many partners (C4's pile-ups: up to
-    // 28) otherwise waits one round trip per PB partners re-read from memory
+    // the next batch, or two, in flight under this batch's solves (UpdateForm PIPE, DEEP)
     [[maybe_unused]] int32_t jn[PB], jn2[PB];
     [[maybe_unused]] Snap<T> sn_next[PB], sn_next2[PB];
-    constexpr bool pipe = !BOXES && RB_SOLVE_PIPE && PM != 1;   // (the cooperative form: LDS only)
-    constexpr bool deep = pipe && SDEPTH > 1;
+    constexpr bool pipe = U::PIPE, deep = U::DEEP;
     if constexpr (pipe) {
         if (np_ > 0) fetch(0, jn, sn_next);
         if constexpr (deep)
@@ -530,12 +619,7 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     // atomic would wait for every older store), its round trip overlaps the
     // snapshot store and the quaternion update
     Claim cl{0u, 0, 0ull, 0u, 0};
-    // the one-lane and wide forms (and the split form's update) run in
-    // linear-layout worlds only; the cooperative form and the box kernel
-    // read the layout
-    constexpr int L = (PM == 2 || (PM == 0 && !BOXES)) ? LAYOUT_LINEAR : LAYOUT_ANY;
-    // heads per line: known in the cooperative and wide forms (rb_api_world.hip)
-    constexpr int RL = PM == 1 ? 0 : PM == 2 ? 2 : -1;
+    constexpr int L = U::L, RL = U::RL;         // the insert's layout and heads per line
     const Table<T> &next = nx.tab ? *nx.tab : p.next;
     if (next.line) cl = claim_slot<L, RL>(p.grid, next, p.err, sn, nx.gen, nx.keep);
     wt_store(p.snap_next + i, sn);
@@ -574,20 +658,30 @@ __device__ __forceinline__ void body_update(const StepParams<T> &p, int32_t l, i
     STAMP(6);
 }
 
+// The helper wave's hand-over to the body wave through LDS: one record per
+// body in column layout (row r of body h at o[r * NB], o = base + h), written
+// by help_body and by the helper wave of the MAXP 32 shared search, read by
+// body_step.  Rows: inv(I_w) 9, v 3, w 3, the recorded plane contacts 1
+// (HELP_NO_PLANES: the planes are not solved), q 4, m 1.  (The three places
+// index the rows in line: a store or load function of the record changes the
+// wide unit's instruction order, profiles/step_forms/README.md)
+enum : int { HELP_INVI = 0, HELP_V = 9, HELP_W = 12, HELP_NREC = 15, HELP_Q = 16, HELP_M = 20, HELP_REALS = 21 };
+constexpr int HELP_NO_PLANES = -1;
+
 // One body (G lanes): contact search, then (lane 0) the update.  WIDE: the
 // one-lane form for one wave per SIMD (search_buckets_wide; state loads and
 // inv(I_w) under the head loads).
-template <typename T, int MAXP, int G, bool WIDE, bool BOXES, bool PRE = false, bool HELP = false, bool EP = false,
-          bool SHARE = false>
+template <typename T, typename F>
 __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> &ld, bool active, int64_t lb, int slot,
                                           int k, int tid,
                                           int32_t *s_id, Snap<T> *s_pos, int32_t *t_id, Snap<T> *t_pos,
                                           uint32_t *s_cand, int32_t *cell, uint32_t gen, T *s_poly,
-                                          uint8_t *s_didx = nullptr, Snap<T> *s_hpos = nullptr,
-                                          T *s_help = nullptr, int role = 0, uint32_t *s_half = nullptr,
-                                          uint32_t ctrl = 0u /* PRE && EP: the step's epoch control word */) {
-    static_assert(!SHARE || (G == 1 && WIDE && HELP && !BOXES), "shared search: the helper-wave wide form");
-    constexpr int NB = STEP_BLOCK / G;
+                                          uint8_t *s_didx, Snap<T> *s_hpos, T *s_help, int role, uint32_t *s_half,
+                                          uint32_t ctrl /* PRE && EP: the step's epoch control word */) {
+    using FT = FormTraits<F>;
+    constexpr int MAXP = F::MAXP, G = F::G, NB = FT::NB;
+    constexpr bool WIDE = F::WIDE, BOXES = F::BOXES, PRE = F::PRE, HELP = F::HELP, EP = F::EP, SHARE = F::SHARE;
+    constexpr bool LATE = FT::LATE, early = FT::EARLY, FIN = FT::FIN, work2 = FT::WORK2;
     const int32_t l = active ? (int32_t)lb : 0;
     const int32_t i = ld.lo + l;
 
@@ -595,12 +689,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     const Snap<T> self = xld(ld.snap_cur + i);
     const V3<T> x = {self.x, self.y, self.z};
     const int32_t ci = RB_ABLATE == 8 ? 0 : i;    // (diagnostic, load_body)
-    // worlds with epochs, shared search: the kind-dependent selects below are
-    // made under the head loads (late_kind, called by the search's overlap):
-    // the wait for kind, sy and sz counts loads in issue order, so ahead of
-    // the heads it would hold them back until the finishing wave's state
-    // loads, issued after these, had landed
-    constexpr bool LATE = SHARE && EP;
+    // (LATE: the kind-dependent selects below wait for the search's overlap)
     int32_t kind = ld.cs.kind[ci];
     const T bi = self.r;
     // half extents y, z only matter for boxes; loaded for every body (a load
@@ -617,9 +706,7 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     BodyIn<T> in;
     LazyInvI<T> invI;
     bool forced = false;
-    // state loads issued before the search (the wide form measured 5 % slower
-    // with them issued after the bucket heads, C3)
-    constexpr bool early = G > 1 || WIDE;
+    // (early: the state loads issued before the search)
     if constexpr (SHARE) {
         // both waves run this function (role 1: the helper wave, lane t for
         // the body of body lane t); the helper loads the state and constants
@@ -674,7 +761,6 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     // age 0: the step before built that table from every body, once each
     [[maybe_unused]] bool ep_appended = false;
     if constexpr (EP) {
-        static_assert(PRE && WIDE, "append epochs: the wide step kernels");
         {
             const uint32_t cw = ctrl;                // (== *p.ep.ctrl: the lead block's word of this parity)
             const uint32_t t = cw & EP_TAB;
@@ -696,8 +782,6 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
     // what a helper wave has done for the body already (HelpDone)
     bool help_planes = false;
     int32_t help_nrec = 0;
-    // shared search: the helper wave finishes the body (below)
-    constexpr bool FIN = SHARE && share_finish<MAXP>();
     if constexpr (SHARE) {
         // the search shared between the two waves (rb_grid.hpp
         // search_half_wide): the body wave five of the eight buckets, the helper three.  The helper
@@ -710,7 +794,6 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         int32_t hrec = 0;
         bool hplanes = false;
         // gravity and the plane contacts (not with applied forces: body_update's)
-        constexpr bool work2 = MAXP > 16 ? RB_SHARE_WORK2_32 != 0 : RB_SHARE_WORK2 != 0;
         auto own_planes = [&] {
             if (p.xfrc) return;
             apply_force(p, l, in.m, invI, in.v, in.w);
@@ -766,12 +849,13 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
             if (role && active) {
                 T *o = s_help + tid;
 #pragma unroll
-                for (int e = 0; e < 9; ++e) o[e * NB] = hm.a[e];
-                o[9 * NB] = in.v.x; o[10 * NB] = in.v.y; o[11 * NB] = in.v.z;
-                o[12 * NB] = in.w.x; o[13 * NB] = in.w.y; o[14 * NB] = in.w.z;
-                o[15 * NB] = T(hplanes ? hrec : -1);
-                o[16 * NB] = in.q.w; o[17 * NB] = in.q.x; o[18 * NB] = in.q.y; o[19 * NB] = in.q.z;
-                o[20 * NB] = in.m;
+                for (int e = 0; e < 9; ++e) o[(HELP_INVI + e) * NB] = hm.a[e];
+                o[HELP_V * NB] = in.v.x; o[(HELP_V + 1) * NB] = in.v.y; o[(HELP_V + 2) * NB] = in.v.z;
+                o[HELP_W * NB] = in.w.x; o[(HELP_W + 1) * NB] = in.w.y; o[(HELP_W + 2) * NB] = in.w.z;
+                o[HELP_NREC * NB] = T(hplanes ? hrec : HELP_NO_PLANES);
+                o[HELP_Q * NB] = in.q.w; o[(HELP_Q + 1) * NB] = in.q.x; o[(HELP_Q + 2) * NB] = in.q.y;
+                o[(HELP_Q + 3) * NB] = in.q.z;
+                o[HELP_M * NB] = in.m;
             }
             __syncthreads();
             if (role) return;
@@ -837,21 +921,21 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         const T *o = s_help + slot;
         constexpr int NBH = STEP_BLOCK / G;
 #pragma unroll
-        for (int e = 0; e < 9; ++e) invI.m.a[e] = o[e * NBH];
+        for (int e = 0; e < 9; ++e) invI.m.a[e] = o[(HELP_INVI + e) * NBH];
         invI.have = true;
         if (!p.xfrc) {
-            in.v = {o[9 * NBH], o[10 * NBH], o[11 * NBH]};
-            in.w = {o[12 * NBH], o[13 * NBH], o[14 * NBH]};
+            in.v = {o[HELP_V * NBH], o[(HELP_V + 1) * NBH], o[(HELP_V + 2) * NBH]};
+            in.w = {o[HELP_W * NBH], o[(HELP_W + 1) * NBH], o[(HELP_W + 2) * NBH]};
             forced = true;
         } else if constexpr (WIDE) {             // applied forces: the body lanes apply them
             in.v = {p.st.vx()[l], p.st.vy()[l], p.st.vz()[l]};
             in.w = {p.st.wx()[l], p.st.wy()[l], p.st.wz()[l]};
         }
         if constexpr (WIDE) {
-            in.q = {o[16 * NBH], o[17 * NBH], o[18 * NBH], o[19 * NBH]};
-            in.m = o[20 * NBH];
+            in.q = {o[HELP_Q * NBH], o[(HELP_Q + 1) * NBH], o[(HELP_Q + 2) * NBH], o[(HELP_Q + 3) * NBH]};
+            in.m = o[HELP_M * NBH];
         }
-        const T pr = o[15 * NBH];
+        const T pr = o[HELP_NREC * NBH];
         help_planes = pr >= T(0);
         help_nrec = help_planes ? (int32_t)pr : 0;
     }
@@ -868,9 +952,8 @@ __device__ __forceinline__ void body_step(const StepParams<T> &p, const Lead<T> 
         STAMP(7);
         if (RB_ABLATE == 7) np_ = 0;
     }
-    constexpr int PM = G > 1 ? 1 : (WIDE && RB_WIDE_LDSPOS) ? 2 : 0;
-    constexpr int SD = (WIDE && HELP) ? RB_SOLVE_DEPTH : 1;
-    body_update<T, PM, BOXES, SD, EP>(
+    constexpr int PM = FT::PM;
+    body_update<T, typename FT::Update>(
         p, l, i, x, kind, sz, bi, in, forced, invI,
         Partners<T>{np_, s_id + slot, NB, PM == 2 ? s_hpos + slot : s_pos + slot, PM == 2 ? s_didx + slot : nullptr},
         HelpDone{help_nrec, help_planes}, NextTable<T>{gen_next, EP ? &next : nullptr, ep_append ? b0 : NO_BUCKET},
@@ -911,14 +994,13 @@ __device__ __forceinline__ void fold_bounds(int32_t *bounds, const int32_t *cell
 // workgroup evaluates inv(I_w), gravity and a sphere's plane contacts (the
 // first in its contact order) — VALU chain the body lanes otherwise run
 // under or after their bucket loads — and leaves inv(I_w), v, w and the
-// recorded-contact count, q and m in LDS (column layout, HELP_REALS per body) before
+// recorded-contact count, q and m in LDS (the HELP_* rows, HELP_REALS per body) before
 // the search's first barrier; it then takes part in the search's two
 // barriers.  The same arithmetic in the same order, so bit-identical.
 //
 // WIDE (step_kernel_wide_help): the results go to the body wave's candidate
 // list area once its search is done with it (between the two barriers),
 // so the workgroup's LDS stays within a quarter of the CU's.
-constexpr int HELP_REALS = 21;                   // inv(I_w) 9, v 3, w 3, records 1, q 4, m 1
 template <typename T, int NB, bool WIDE = false>
 __device__ __forceinline__ void help_body(const StepParams<T> &p, const Lead<T> &ld, int h, T *s_help) {
     // the same block -> bodies mapping as the body lanes (step_body)
@@ -959,28 +1041,28 @@ __device__ __forceinline__ void help_body(const StepParams<T> &p, const Lead<T> 
     if (act) {
         T *o = s_help + h;
 #pragma unroll
-        for (int e = 0; e < 9; ++e) o[e * NB] = m.a[e];
-        o[9 * NB] = in.v.x; o[10 * NB] = in.v.y; o[11 * NB] = in.v.z;
-        o[12 * NB] = in.w.x; o[13 * NB] = in.w.y; o[14 * NB] = in.w.z;
-        o[15 * NB] = T(planes ? nrec : -1);
-        o[16 * NB] = in.q.w; o[17 * NB] = in.q.x; o[18 * NB] = in.q.y; o[19 * NB] = in.q.z;
-        o[20 * NB] = in.m;
+        for (int e = 0; e < 9; ++e) o[(HELP_INVI + e) * NB] = m.a[e];
+        o[HELP_V * NB] = in.v.x; o[(HELP_V + 1) * NB] = in.v.y; o[(HELP_V + 2) * NB] = in.v.z;
+        o[HELP_W * NB] = in.w.x; o[(HELP_W + 1) * NB] = in.w.y; o[(HELP_W + 2) * NB] = in.w.z;
+        o[HELP_NREC * NB] = T(planes ? nrec : HELP_NO_PLANES);
+        o[HELP_Q * NB] = in.q.w; o[(HELP_Q + 1) * NB] = in.q.x; o[(HELP_Q + 2) * NB] = in.q.y;
+        o[(HELP_Q + 3) * NB] = in.q.z;
+        o[HELP_M * NB] = in.m;
     }
     __syncthreads();
     if (!WIDE) __syncthreads();                  // search_coop's two barriers
 }
 
-// HALO: the halo push compiled in (checked at run time: p.halo.mail); the
-// wide forms — the single-GPU bench's kernels — are also instantiated
-// without it (launch_step_wide picks), which measured 1-2 % faster at C3
-// SHARE: the helper wave of the wide form also searches half of each body's
-// neighbourhood (body_step; rb_grid.hpp search_half_wide) and then finishes
-// the body — merge, solves, integration, insert and this function's tail —
-// from its own registers; the body wave only searches
-template <typename T, int MAXP, int G, bool WIDE = false, bool BOXES = false, bool HELP = false, bool HALO = true,
-          bool EP = false, bool SHARE = false>
+// A step kernel of form F.  HALO: the halo push compiled in (checked at run
+// time: p.halo.mail); the wide forms — the single-GPU bench's kernels — are
+// also instantiated without it (launch_step_wide picks), which measured
+// 1-2 % faster at C3.  Not a member of the form: body_step does not depend on
+// it, and the kernels that differ only in it share one body_step.
+template <typename T, typename F, bool HALO = true>
 __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> &ld) {
-    constexpr int NB = STEP_BLOCK / G;          // bodies per workgroup
+    constexpr int MAXP = F::MAXP, G = F::G, NB = FormTraits<F>::NB;
+    constexpr bool WIDE = F::WIDE, BOXES = F::BOXES, HELP = F::HELP, EP = F::EP, SHARE = F::SHARE;
+    static_assert(!EP || !HALO, "append epochs: never halo-exchanging");
     __shared__ int32_t s_id[MAXP * NB];
     __shared__ T s_poly[BOXES ? 48 * NB : 1];   // box-box face clipping: 2 x 8 vertices x 3 per body
     __shared__ uint32_t s_cand[WIDE ? WIDE_MAXC * NB : 1];
@@ -1000,7 +1082,6 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     const int tid = SHARE ? (int)(threadIdx.x % STEP_BLOCK) : (int)threadIdx.x;
     if (RB_ABLATE == 3) return;
     if constexpr (HELP && !SHARE) {
-        static_assert(!BOXES, "helper waves: the sphere step kernels");
         if (tid >= STEP_BLOCK) {                 // the workgroup's second wave
             help_body<T, NB, WIDE>(p, ld, tid - STEP_BLOCK, help_lds);
             return;
@@ -1035,13 +1116,13 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
     const bool active = lb < ld.n_local;
     int32_t cell[6] = {INT32_MAX, 0, 0, 0, 0, 0};   // new cell, step-start cell (peer-to-peer exchange)
     if (G > 1 || HELP || active)                 // (a helper's barriers: every lane)
-        body_step<T, MAXP, G, WIDE, BOXES, true, HELP, EP, SHARE>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos,
+        body_step<T, F>(p, ld, active, lb, slot, k, tid, s_id, s_pos, t_id, t_pos,
                                                               s_cand, cell, lw.gen, s_poly, s_didx, s_hpos, help_lds, role,
                                                               s_half, lw.ctrl);
     // shared search: the body wave is done; the helper wave, which finished
     // the bodies, holds their cells and does the rest (its tid 0: block 0's stores)
     // (MAXP 32 instances: the body wave finishes and the helper is done)
-    if (SHARE && (share_finish<MAXP>() ? !role : role)) return;
+    if (SHARE && (FormTraits<F>::FIN ? !role : role)) return;
     if (p.bounds) fold_bounds(p.bounds, cell);
     if (HALO && p.halo.mail) {                   // halo-exchanging shard: push to the peers
         int32_t b[6];
@@ -1081,5 +1162,16 @@ __device__ __forceinline__ void step_body(const StepParams<T> &p, const Lead<T> 
         if (p.epoch) *p.epoch += 1;
     }
 }
+
+// The launchers' dispatch: pick(f, b...) calls f with each run-time choice b
+// as a compile-time constant (std::true_type or std::false_type), so a
+// launcher names a kernel family once and every instance of it is compiled.
+// maxp_c: the partner bound of a "maxp <= 16" choice.
+template <typename Fn> inline void pick(Fn f) { f(); }
+template <typename Fn, typename... Bs> inline void pick(Fn f, bool b, Bs... bs) {
+    if (b) pick([&](auto... c) { f(std::true_type{}, c...); }, bs...);
+    else pick([&](auto... c) { f(std::false_type{}, c...); }, bs...);
+}
+constexpr int maxp_c(bool small) { return small ? 16 : 32; }
 
 }  // namespace rb

@@ -1,6 +1,8 @@
 // rb_step_wide.hip — the wide forms of the step kernel (one lane per body at
 // one wave per SIMD, with and without a helper wave; the body: rb_step.hpp)
-// and their launcher.  A unit of their own because they are built with the
+// and their launcher.  Each kernel names its form (rb_step.hpp FormDefaults:
+// Wide, WideHelp, WideEp, WideHelpEp) and, beside it, whether the halo push
+// is compiled in.  A unit of their own because they are built with the
 // memory-clause scheduling flags (Makefile KFLAGS); rb_internal.hpp declares
 // launch_step_wide extern, so no other unit can compile a copy.
 // Built once per real type: RB_INST = 1 fp64, 2 fp32.
@@ -35,10 +37,8 @@ namespace rb {
 // one wave per SIMD (up to 64 x 1024 owned bodies): every register is free
 template <typename T, int MAXP, bool HALO>
 __global__ __launch_bounds__(STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void step_kernel_wide(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                      const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, false, HALO>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
+void step_kernel_wide(LEAD_PARAMS(T), StepParams<T> p) {
+    step_body<T, Wide<MAXP>, HALO>(p, LEAD_OF(T));
 }
 
 // the wide form with a helper wave per workgroup (help_body): two waves per
@@ -47,10 +47,8 @@ void step_kernel_wide(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T
 // neighbourhood (rb_grid.hpp search_half_wide) and finish the body
 template <typename T, int MAXP, bool HALO, bool SHARE>
 __global__ __launch_bounds__(2 * STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void step_kernel_wide_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, const T *cs_base, int64_t cs_Npad,
-                           const int32_t *cs_kind, int32_t n_local, int32_t lo, StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, true, HALO, false, SHARE>(
-        p, Lead<T>{snap_cur, BodyState<T>{st_base, st_S}, BodyConsts<T>{cs_base, cs_Npad, cs_kind}, n_local, lo});
+void step_kernel_wide_help(LEAD_PARAMS(T), StepParams<T> p) {
+    step_body<T, WideHelp<MAXP, SHARE>, HALO>(p, LEAD_OF(T));
 }
 
 // The instances of worlds with append epochs (never halo-exchanging): the
@@ -59,12 +57,12 @@ void step_kernel_wide_help(const Snap<T> *snap_cur, T *st_base, int64_t st_S, co
 template <typename T, int MAXP>
 __global__ __launch_bounds__(STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void step_kernel_wide_ep(LEAD_EP_PARAMS(T), StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, false, false, true>(p, LEAD_EP_OF(T));
+    step_body<T, WideEp<MAXP>, false>(p, LEAD_EP_OF(T));
 }
 template <typename T, int MAXP, bool SHARE>
 __global__ __launch_bounds__(2 * STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void step_kernel_wide_help_ep(LEAD_EP_PARAMS(T), StepParams<T> p) {
-    step_body<T, MAXP, 1, true, false, true, false, true, SHARE>(p, LEAD_EP_OF(T));
+    step_body<T, WideHelpEp<MAXP, SHARE>, false>(p, LEAD_EP_OF(T));
 }
 
 template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int maxp, bool help, bool share, hipStream_t s) {
@@ -74,42 +72,22 @@ template <typename T> hipError_t launch_step_wide(const StepParams<T> &p, int ma
     // worlds with append epochs (never halo-exchanging: rb_api_step.hip
     // epoch_eligible) launch the instantiation that carries the epoch code
     const bool ep = p.ep.ctrl != nullptr && !halo;
-#define RB_WIDE_LAUNCH(K, M, H, TH)                                                                               \
-    hipLaunchKernelGGL((K<T, M, H>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p)
-#define RB_WIDE_HELP_EP_LAUNCH(M, TH)                                                                             \
-    do {                                                                                                          \
-        if (share) hipLaunchKernelGGL((step_kernel_wide_help_ep<T, M, true>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_EP_ARGS(p), p); \
-        else hipLaunchKernelGGL((step_kernel_wide_help_ep<T, M, false>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_EP_ARGS(p), p); \
-    } while (0)
-#define RB_WIDE_HELP_LAUNCH(M, H, TH)                                                                             \
-    do {                                                                                                          \
-        if (share) hipLaunchKernelGGL((step_kernel_wide_help<T, M, H, true>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p); \
-        else hipLaunchKernelGGL((step_kernel_wide_help<T, M, H, false>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_ARGS(p), p); \
-    } while (0)
-#define RB_WIDE_PICK(K, M, TH)                                                                                    \
-    do {                                                                                                          \
-        if (halo) RB_WIDE_LAUNCH(K, M, true, TH);                                                                 \
-        else if (ep) hipLaunchKernelGGL((K##_ep<T, M>), dim3((unsigned)blocks), dim3(TH), 0, s, LEAD_EP_ARGS(p), p); \
-        else RB_WIDE_LAUNCH(K, M, false, TH);                                                                     \
-    } while (0)
-    if (help) {
-#define RB_WIDE_HELP_PICK(M)                                                                                      \
-    do {                                                                                                          \
-        if (halo) RB_WIDE_HELP_LAUNCH(M, true, 2 * STEP_BLOCK);                                                   \
-        else if (ep) RB_WIDE_HELP_EP_LAUNCH(M, 2 * STEP_BLOCK);                                                   \
-        else RB_WIDE_HELP_LAUNCH(M, false, 2 * STEP_BLOCK);                                                       \
-    } while (0)
-        if (maxp <= 16) RB_WIDE_HELP_PICK(16);
-        else RB_WIDE_HELP_PICK(32);
-#undef RB_WIDE_HELP_PICK
-#undef RB_WIDE_HELP_LAUNCH
-#undef RB_WIDE_HELP_EP_LAUNCH
-        return hipGetLastError();
-    }
-    if (maxp <= 16) RB_WIDE_PICK(step_kernel_wide, 16, STEP_BLOCK);
-    else RB_WIDE_PICK(step_kernel_wide, 32, STEP_BLOCK);
-#undef RB_WIDE_PICK
-#undef RB_WIDE_LAUNCH
+    const dim3 grid((unsigned)blocks), one(STEP_BLOCK), two(2 * STEP_BLOCK);
+    const bool m16 = maxp <= 16;
+    // (the choices in this order, and the _ep kernels between the two halo
+    // choices: the order the instances are compiled in)
+    if (help)
+        pick([&](auto m, auto h, auto e, auto sh) {
+            constexpr int M = maxp_c(m.value);
+            if constexpr (e.value && !h.value) hipLaunchKernelGGL((step_kernel_wide_help_ep<T, M, sh.value>), grid, two, 0, s, LEAD_EP_ARGS(p), p);
+            else hipLaunchKernelGGL((step_kernel_wide_help<T, M, h.value, sh.value>), grid, two, 0, s, LEAD_ARGS(p), p);
+        }, m16, halo, ep, share);
+    else
+        pick([&](auto m, auto h, auto e) {
+            constexpr int M = maxp_c(m.value);
+            if constexpr (e.value && !h.value) hipLaunchKernelGGL((step_kernel_wide_ep<T, M>), grid, one, 0, s, LEAD_EP_ARGS(p), p);
+            else hipLaunchKernelGGL((step_kernel_wide<T, M, h.value>), grid, one, 0, s, LEAD_ARGS(p), p);
+        }, m16, halo, ep);
     return hipGetLastError();
 }
 

@@ -77,7 +77,10 @@ def test_wide_help_fp64_fits_two_waves_per_simd(step_asm):
     """The wide + helper fp64 instances run two waves per SIMD: at most 256
     registers each.  The counts before the lead block, for the report:
     profiles/help_finish/resources_wide.txt (194-244), whose names carry the
-    flags <MAXP, HALO, EP, SHARE>; the EP instances are the _ep kernels now."""
+    flags <MAXP, HALO, EP, SHARE>; the EP instances are the _ep kernels now.
+    (The kernels' own parameters are still <MAXP, HALO, SHARE> and, for the
+    _ep kernels, <MAXP, SHARE>; inside, a form type names them: rb_step.hpp
+    WideHelp<MAXP, SHARE> and WideHelpEp<MAXP, SHARE>, HALO beside the form.)"""
     txt = open(os.path.join(ROOT, "profiles", "help_finish", "resources_wide.txt")).read()
     base = {}
     for m in re.finditer(r"Function Name: _ZN2rb21step_kernel_wide_helpIdLi(\d+)ELb([01])ELb([01])ELb([01])EE\S+\s+"
