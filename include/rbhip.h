@@ -346,10 +346,11 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * An environment steps bit-identically to an rb_world of the same scene,
  * under either contact law (rb_batch_set_contact_law).
  * Arrays are environment-major: body k of environment e at row e*M + k.
- * Not covered (use rb_world): contact recording, sharding,
+ * Not covered (use rb_world): contacts recorded inside a step (a batch is
+ * asked for the contact list of its current state: rb_batch_contacts), sharding,
  * per-environment kinds or plane counts, more than 64 bodies per
- * environment; under RB_LAW_BALLS also per-environment planes and applied
- * forces.
+ * environment; under RB_LAW_BALLS also per-environment planes, applied
+ * forces and the contact query.
  * A batch handle is not thread-safe; every call that takes host arrays is
  * synchronous (the device-resident boundary below only enqueues).
  *
@@ -540,6 +541,62 @@ int  rb_batch_status_dev(rb_batch *b, int32_t *code, int64_t *steps_done);
 int  rb_batch_run_sampled_dev(rb_batch *b, int64_t nsteps, int64_t every, double dt,
                               double restitution, double friction, double contact_threshold,
                               void *qpos, void *qvel, int32_t io_dtype);
+
+/* ---- the contact query of a batch (additive to librbhip 0.4) -------------------
+ * For the batch's current state, each body's contact list exactly as
+ * mj_forward generates it for that environment's scene: what the reference
+ * reads as data.contact[i].dist / pos / frame / geom1 / geom2 (collision.py:57,
+ * :72-76), per environment.  A pure function of the state and the batch's
+ * constants (sizes, planes per environment where rb_batch_set_planes is set):
+ * it steps nothing and changes nothing.  The list holds every generated
+ * contact; the skip rules of the step (dist < 0, the contact threshold) are
+ * not applied.
+ *
+ * Order (the canonical per-body order of rb_get_contacts): the planes in plane
+ * order, a sphere's one contact per plane, a box's corners in bit order with
+ * at most 4 per plane; then the other bodies of the environment by ascending
+ * id, a box pair's points in generation order.
+ *
+ * Layout: dense, R = max_records slots per body.  counts [n][M]; partner, kind
+ * and dist [n][M][R]; pos and frame [n][M][R][3].  counts[t][k] is the true
+ * number of contacts of body k of listed environment t, also where it exceeds
+ * R: the records past R are dropped, the first R kept.  A record: partner = the
+ * other body's id within the environment, or -1 - plane; kind = RB_CK_*; dist,
+ * pos and frame as MuJoCo's mjContact has them.  frame is the raw normal from
+ * geom1 to geom2 (as rb_kat_narrow reports it; no normal convention applied).
+ * geom1 is the plane of a plane contact; the lower id of two spheres or of two
+ * boxes; the sphere of a sphere-box pair.  Slots at or past the count hold
+ * kind -1 and zeros elsewhere, so every word of the output is defined.  An
+ * environment whose status is failed (rb_batch_status) has count -1 for each
+ * of its bodies, and unused slots only.
+ *
+ * pos and frame may be NULL, together or singly.  partner, kind and dist may
+ * be NULL only all together, with max_records 0: a counts-only query.  counts
+ * is required.
+ *
+ * RB_EINVAL, with nothing enqueued: max_records < 0; max_records 0 with a
+ * record array given, or > 0 without; n < 0; env_ids out of range or listing
+ * an environment twice; in the device form a host pointer or memory of another
+ * device.  RB_EUNSUPPORTED under RB_LAW_BALLS: that law has no contact list
+ * (its hit test carries a tolerance of its own).
+ *
+ * rb_batch_contacts: host arrays, for the environments env_ids[n] (NULL = all
+ * n_envs in order, n = n_envs), synchronous: like rb_batch_get_state it
+ * finishes the batch's pending work first.  *n_truncated (may be NULL) = the
+ * listed bodies with count > max_records.  The lists are staged in a device
+ * buffer owned by the batch, allocated on first use and freed with it, of at
+ * most RBHIP_BATCH_SAMPLE_BYTES bytes; a request that does not fit is cut into
+ * several launches over ranges of the listed environments (RB_EINVAL if one
+ * environment's lists alone do not fit). */
+int  rb_batch_contacts(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t max_records,
+                       int32_t *counts, int32_t *partner, int32_t *kind,
+                       double *dist, double *pos, double *frame, int64_t *n_truncated);
+/* The same into device arrays of the caller, all environments, enqueued on the
+ * batch's stream without waiting (the rules of the device-resident boundary
+ * above).  dist, pos and frame are of io_dtype (RB_F64 | RB_F32), converted
+ * from the batch's real type by a C cast. */
+int  rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, int32_t *partner,
+                           int32_t *kind, void *dist, void *pos, void *frame, int32_t io_dtype);
 
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do

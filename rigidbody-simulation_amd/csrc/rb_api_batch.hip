@@ -7,6 +7,7 @@
 // only enqueues and rb_batch_sync waits.
 #include <cmath>
 
+#include "rb_batch_contacts.hpp"
 #include "rb_batch_dev.hpp"
 #include "rb_host.hpp"
 #include "rb_sampleplan.hpp"
@@ -55,6 +56,10 @@ struct rb_batch {
     // rb_batch_set_xfrc_dev: the smallest body slot an upload was refused for
     // (DEV_NO_SLOT: none), sticky until rb_batch_sync reports and clears it
     uint32_t *refused = nullptr;
+    // rb_batch_contacts: device staging of the lists of a range of listed
+    // environments (allocated on first use, it only grows, at most samp_limit bytes)
+    char *con = nullptr;
+    size_t con_bytes = 0;
 };
 
 namespace {
@@ -64,7 +69,7 @@ void free_batch(rb_batch *b) {
     (void)hipSetDevice(b->device);
     if (b->own_stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused};
+                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused, b->con};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);   // (never the caller's)
@@ -213,6 +218,18 @@ size_t sample_bytes(const rb_batch *b, int rows) {
     return align8(vals * (size_t)b->esz) + vals * sizeof(double);
 }
 
+// an env_ids list onto the device (b->ids)
+int batch_put_ids(rb_batch *b, const int64_t *env_ids, int64_t n) {
+    if (n > b->ids_cap) {
+        if (b->ids) { HIPCHK(hipFree(b->ids)); b->ids = nullptr; }
+        b->ids_cap = 0;
+        HIPCHK(hipMalloc((void **)&b->ids, sizeof(int64_t) * (size_t)n));
+        b->ids_cap = n;
+    }
+    HIPCHK(hipMemcpyAsync(b->ids, env_ids, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, b->stream));
+    return RB_OK;
+}
+
 // the listed environments' rows: staging of n * M rows and the ids on the device
 int batch_stage(rb_batch *b, const int64_t *env_ids, int64_t n) {
     const int64_t rows = n * b->M;
@@ -224,15 +241,7 @@ int batch_stage(rb_batch *b, const int64_t *env_ids, int64_t n) {
         HIPCHK(hipMalloc((void **)&b->io_v, sizeof(double) * 6 * (size_t)rows));
         b->io_rows = rows;
     }
-    if (env_ids) {
-        if (n > b->ids_cap) {
-            if (b->ids) { HIPCHK(hipFree(b->ids)); b->ids = nullptr; }
-            b->ids_cap = 0;
-            HIPCHK(hipMalloc((void **)&b->ids, sizeof(int64_t) * (size_t)n));
-            b->ids_cap = n;
-        }
-        HIPCHK(hipMemcpyAsync(b->ids, env_ids, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, b->stream));
-    }
+    if (env_ids) WCHK(batch_put_ids(b, env_ids, n));
     return RB_OK;
 }
 
@@ -388,6 +397,34 @@ int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mi
     }
     if (int rc = rb_batch_set_bodies(b, mass.data(), inertia.data(), size.data())) return bail(rc);
     *out = b;
+    return RB_OK;
+}
+
+// ---- the contact query (rb_batch_contacts, rb_batch_contacts_dev) ---------------
+// the arguments both forms share, before any device call
+int batch_check_contacts(const rb_batch *b, int32_t R, const void *counts, const void *partner, const void *kind,
+                         const void *dist, const void *pos, const void *frame) {
+    if (!b) return fail(RB_EINVAL, "null batch");
+    if (R < 0) return fail(RB_EINVAL, "max_records < 0");
+    if (!counts) return fail(RB_EINVAL, "counts NULL");
+    const int given = (partner != nullptr) + (kind != nullptr) + (dist != nullptr);
+    if (given != 0 && given != 3) return fail(RB_EINVAL, "partner, kind and dist may be NULL only all together");
+    if (R == 0 && (given || pos || frame)) return fail(RB_EINVAL, "max_records 0 with record arrays given");
+    if (R > 0 && !given) return fail(RB_EINVAL, "max_records %d with partner, kind and dist NULL (a counts-only query has max_records 0)", R);
+    return RB_OK;
+}
+int batch_check_contact_law(const rb_batch *b) {
+    if (b->law == RB_LAW_BALLS)
+        return fail(RB_EUNSUPPORTED, "the two-ball law has no contact list (its hit test carries a tolerance of its own)");
+    return RB_OK;
+}
+
+// one launch of the query: rows [0, q.n) of q
+int batch_launch_contacts(rb_batch *b, const ContactQuery &q) {
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_batch_contacts<T>(batch_params<T>(b, 0, 1.0, 0.0, 0.0, 0.0), q, b->mixed, b->stream);
+    }));
     return RB_OK;
 }
 
@@ -787,6 +824,104 @@ int rb_batch_run_sampled_dev(rb_batch *b, int64_t nsteps, int64_t every, double 
         }));
     }
     return RB_OK;
+}
+
+// ---- the contact query ----------------------------------------------------------
+
+int rb_batch_contacts(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t max_records, int32_t *counts,
+                      int32_t *partner, int32_t *kind, double *dist, double *pos, double *frame, int64_t *n_truncated) {
+    ApiScope api_scope_(b ? b->device : -1);
+    const int32_t R = max_records;
+    WCHK(batch_check_contacts(b, R, counts, partner, kind, dist, pos, frame));
+    if (n < 0) return fail(RB_EINVAL, "n < 0");
+    WCHK(batch_check_ids(b, env_ids, n));
+    if (env_ids) {
+        std::vector<int64_t> sorted(env_ids, env_ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return fail(RB_EINVAL, "env_ids lists environment %lld twice", (long long)*dup);
+    }
+    WCHK(batch_check_contact_law(b));
+    if (n_truncated) *n_truncated = 0;
+    if (n == 0) return RB_OK;
+    // one listed environment in the staging buffer: the reals first (aligned), then the words
+    const size_t M = (size_t)b->M, MR = M * (size_t)R;
+    const size_t per = sizeof(double) * MR * (1 + (pos ? 3 : 0) + (frame ? 3 : 0)) + sizeof(int32_t) * (M + 2 * MR);
+    if (per > b->samp_limit)
+        return fail(RB_EINVAL, "the contact lists of one environment (%zu bytes) do not fit the staging buffer (%zu bytes: "
+                               "RBHIP_BATCH_SAMPLE_BYTES)", per, b->samp_limit);
+    const int64_t fit = std::min<int64_t>(n, (int64_t)(b->samp_limit / per));
+    HIPCHK(hipSetDevice(b->device));
+    if (per * (size_t)fit > b->con_bytes) {
+        if (b->con) { HIPCHK(hipFree(b->con)); b->con = nullptr; }
+        b->con_bytes = 0;
+        HIPCHK(hipMalloc((void **)&b->con, per * (size_t)fit));
+        b->con_bytes = per * (size_t)fit;
+    }
+    if (env_ids) WCHK(batch_put_ids(b, env_ids, n));
+    // a range of listed environments per launch
+    for (int64_t first = 0; first < n; first += fit) {
+        const size_t c = (size_t)std::min<int64_t>(fit, n - first), at = (size_t)first;
+        double *d_dist = reinterpret_cast<double *>(b->con);
+        double *d_pos = d_dist + c * MR, *d_frame = d_pos + (pos ? 3 * c * MR : 0);
+        int32_t *d_counts = reinterpret_cast<int32_t *>(d_frame + (frame ? 3 * c * MR : 0));
+        int32_t *d_partner = d_counts + c * M, *d_kind = d_partner + c * MR;
+        ContactQuery q{};
+        q.counts = d_counts;
+        if (R > 0) { q.partner = d_partner; q.kind = d_kind; q.dist = d_dist; }
+        q.pos = pos ? d_pos : nullptr;
+        q.frame = frame ? d_frame : nullptr;
+        q.ids = env_ids ? b->ids + first : nullptr;
+        q.env0 = first;
+        q.n = (int64_t)c;
+        q.R = R;
+        q.io32 = 0;
+        q.box = b->box;
+        WCHK(batch_launch_contacts(b, q));
+        const auto get = [&](void *dst, const void *src, size_t bytes) {
+            return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
+        };
+        HIPCHK(get(counts + at * M, d_counts, sizeof(int32_t) * c * M));
+        if (R > 0) {
+            HIPCHK(get(partner + at * MR, d_partner, sizeof(int32_t) * c * MR));
+            HIPCHK(get(kind + at * MR, d_kind, sizeof(int32_t) * c * MR));
+            HIPCHK(get(dist + at * MR, d_dist, sizeof(double) * c * MR));
+            if (pos) HIPCHK(get(pos + 3 * at * MR, d_pos, sizeof(double) * 3 * c * MR));
+            if (frame) HIPCHK(get(frame + 3 * at * MR, d_frame, sizeof(double) * 3 * c * MR));
+        }
+        HIPCHK(hipStreamSynchronize(b->stream));     // (the next range reuses the staging buffer)
+    }
+    if (n_truncated) {
+        int64_t t = 0;
+        for (size_t k = 0; k < (size_t)n * M; ++k) t += counts[k] > R;
+        *n_truncated = t;
+    }
+    return RB_OK;
+}
+
+int rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, int32_t *partner, int32_t *kind,
+                          void *dist, void *pos, void *frame, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    WCHK(batch_check_contacts(b, max_records, counts, partner, kind, dist, pos, frame));
+    WCHK(batch_check_io(io_dtype));
+    WCHK(batch_check_contact_law(b));
+    HIPCHK(hipSetDevice(b->device));
+    const std::pair<const void *, const char *> arrays[] = {{counts, "counts"}, {partner, "partner"}, {kind, "kind"},
+                                                            {dist, "dist"},     {pos, "pos"},         {frame, "frame"}};
+    for (const auto &a : arrays)
+        if (a.first) WCHK(batch_dev_ptr(b, a.first, a.second));
+    ContactQuery q{};
+    q.counts = counts;
+    q.partner = partner;
+    q.kind = kind;
+    q.dist = dist;
+    q.pos = pos;
+    q.frame = frame;
+    q.n = b->E;
+    q.R = max_records;
+    q.io32 = io_dtype == RB_F32;
+    q.box = b->box;
+    return batch_launch_contacts(b, q);
 }
 
 }  // extern "C"

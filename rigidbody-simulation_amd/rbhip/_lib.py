@@ -98,6 +98,8 @@ SIGNATURES = {
     "rb_batch_set_xfrc_dev": (C.c_int, [_P, _P, _I32]),
     "rb_batch_status_dev": (C.c_int, [_P, _P, _P]),
     "rb_batch_run_sampled_dev": (C.c_int, [_P, _I64, _I64, _D, _D, _D, _D, _P, _P, _I32]),
+    "rb_batch_contacts": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, C.POINTER(_I64)]),
+    "rb_batch_contacts_dev": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32]),
 }
 
 # rb_world_stats indices (include/rbhip.h RB_STAT_*)

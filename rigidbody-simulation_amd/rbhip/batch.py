@@ -65,6 +65,42 @@ def _io_typestr(name, dtype):
     return ts
 
 
+class BatchContacts:
+    """The contact lists of a batch's state (BatchWorld.contacts /
+    contacts_device): dense arrays, R = max_records slots per body.
+
+    counts (n, M) int32: the true number of contacts of each body, also where
+    it exceeds R (then only the first R records are kept); -1 for every body
+    of a failed environment.  partner, kind (n, M, R) int32 and dist (n, M, R):
+    partner is the other body's id within the environment or -1 - plane, kind
+    an RB_CK_* code.  pos, frame (n, M, R, 3), or None without geometry: frame
+    is the raw normal from geom1 to geom2 (geom1: the plane; the lower id of
+    two spheres or two boxes; the sphere of a sphere-box pair).  Slots at or
+    past a body's count hold kind -1 and zeros.  truncated: the number of
+    bodies with count > R (None for the device form, which does not wait).
+    With max_records 0 only counts is set."""
+
+    def __init__(self, max_records, counts, partner, kind, dist, pos, frame, truncated):
+        self.max_records = max_records
+        self.counts, self.partner, self.kind, self.dist = counts, partner, kind, dist
+        self.pos, self.frame = pos, frame
+        self.truncated = truncated
+
+    def lists(self, i: int):
+        """Row i's contacts in the CSR shape of World.contacts(): (counts (M,),
+        partner, kind, dist, pos, frame), the last five flat over the kept
+        records, body by body (pos / frame None without geometry).  Host
+        arrays only."""
+        if self.partner is None:
+            raise ValueError("lists(): a counts-only query (max_records 0) holds no records")
+        cnt = np.asarray(self.counts[i])
+        keep = np.arange(self.max_records)[None, :] < np.minimum(cnt, self.max_records)[:, None]
+
+        def pick(a):
+            return None if a is None else np.asarray(a[i])[keep]
+        return cnt.copy(), pick(self.partner), pick(self.kind), pick(self.dist), pick(self.pos), pick(self.frame)
+
+
 class BatchWorld:
     def __init__(self, scene: Scene, n_envs: int, device: int = 0, dtype: str = "f64",
                  normal_convention: Optional[str] = None, law: str = "mujoco", tol: float = 0.01):
@@ -285,6 +321,39 @@ class BatchWorld:
         _lib.check(self._L.rb_batch_status(self._h, _lib.ptr(code), _lib.ptr(done)), "rb_batch_status")
         return code, done
 
+    # ---- contact lists --------------------------------------------------------
+    def _max_records(self, max_records):
+        """The scene's bound 4 planes' corners + every other body (4 points
+        each in a mixed template), capped at 16."""
+        if max_records is not None:
+            return int(max_records)
+        M, P = self.n_bodies, int(np.shape(self.scene.planes)[0])
+        mixed = M > 1 and bool(np.any(np.asarray(self.scene.kind) != 0))
+        return min(16, 4 * P + (4 if mixed else 1) * (M - 1))
+
+    def contacts(self, envs=None, max_records=None, geometry=True) -> BatchContacts:
+        """The contact list of every body of the environments in envs (None:
+        all) for the batch's current state, as mj_forward generates it for the
+        environment's scene (data.contact, collision.py:57, :72-76), in the
+        canonical order of World.contacts().  It steps nothing and changes
+        nothing.  max_records: slots per body (None: the scene's bound, at
+        most 16; 0: counts only); geometry=False leaves pos and frame out.
+        Not under "balls"."""
+        ids, n = self._envs(envs)
+        R, M = self._max_records(max_records), self.n_bodies
+        counts = np.zeros((n, M), np.int32)
+        rec = R > 0
+        partner = np.zeros((n, M, R), np.int32) if rec else None
+        kind = np.zeros((n, M, R), np.int32) if rec else None
+        dist = np.zeros((n, M, R)) if rec else None
+        pos = np.zeros((n, M, R, 3)) if rec and geometry else None
+        frame = np.zeros((n, M, R, 3)) if rec and geometry else None
+        nt = C.c_int64()
+        _lib.check(self._L.rb_batch_contacts(self._h, _lib.ptr(ids), n, R, _lib.ptr(counts), _lib.ptr(partner),
+                                             _lib.ptr(kind), _lib.ptr(dist), _lib.ptr(pos), _lib.ptr(frame),
+                                             C.byref(nt)), "rb_batch_contacts")
+        return BatchContacts(R, counts, partner, kind, dist, pos, frame, nt.value)
+
     # ---- the device-resident boundary ---------------------------------------
     # Arrays are objects with __cuda_array_interface__ on the batch's device,
     # float64 or float32 whatever the batch's dtype (converted by a cast).
@@ -398,3 +467,51 @@ class BatchWorld:
         _lib.check(self._L.rb_batch_run_sampled_dev(self._h, nsteps, every, *p, qp, vp, _IO_CODES[ts]),
                    "rb_batch_run_sampled_dev")
         return q, v
+
+    def contacts_device(self, max_records=None, geometry=True, dtype=None, out=None) -> BatchContacts:
+        """contacts() of all environments into device memory, enqueued on the
+        batch's stream without waiting: a BatchContacts whose fields are the
+        arrays of `out` (a BatchContacts of an earlier call, or a mapping
+        with the fields' names; its max_records and geometry hold) or new
+        torch tensors: counts, partner and kind int32, dist, pos and frame of
+        `dtype` ("f64" / "f32"; None: the arrays', else the batch's).
+        truncated is None: nothing is read back."""
+        E, M = self.n_envs, self.n_bodies
+        names = ("counts", "partner", "kind", "dist", "pos", "frame")
+        if out is not None:
+            given = {k: (out.get(k) if hasattr(out, "get") else getattr(out, k, None)) for k in names}
+            if given["counts"] is None:
+                raise ValueError("out: counts is required")
+            if given["partner"] is None:
+                R = 0
+            else:
+                try:
+                    R = int(given["partner"].__cuda_array_interface__["shape"][-1])
+                except Exception as exc:
+                    raise TypeError("partner: expected device memory (an object with __cuda_array_interface__), "
+                                    f"got {type(given['partner']).__name__}") from exc
+            if max_records is not None and int(max_records) != R:
+                raise ValueError(f"partner: {R} slots per body, max_records is {int(max_records)}")
+        else:
+            given = dict.fromkeys(names)
+            R = self._max_records(max_records)
+        if R < 0:
+            raise ValueError("max_records < 0")
+        ts = self._pair_typestr(("dist", "pos", "frame"), (given["dist"], given["pos"], given["frame"]), dtype)
+        if out is None:
+            given["counts"] = self._new((E, M), "<i4")
+            if R > 0:
+                given["partner"], given["kind"] = self._new((E, M, R), "<i4"), self._new((E, M, R), "<i4")
+                given["dist"] = self._new((E, M, R), ts)
+                if geometry:
+                    given["pos"], given["frame"] = self._new((E, M, R, 3), ts), self._new((E, M, R, 3), ts)
+        shapes = {"counts": ((E, M), ("<i4",)), "partner": ((E, M, R), ("<i4",)), "kind": ((E, M, R), ("<i4",)),
+                  "dist": ((E, M, R), (ts,)), "pos": ((E, M, R, 3), (ts,)), "frame": ((E, M, R, 3), (ts,))}
+        ptrs = {k: None if given[k] is None else _device_array(k, given[k], *shapes[k], out=True)[0] for k in names}
+        if R > 0 and None in (ptrs["partner"], ptrs["kind"], ptrs["dist"]):
+            raise ValueError("partner, kind and dist: all three are required with max_records > 0")
+        _lib.check(self._L.rb_batch_contacts_dev(self._h, R, *(ptrs[k] for k in names), _IO_CODES[ts]),
+                   "rb_batch_contacts_dev")
+        if R == 0:
+            return BatchContacts(0, given["counts"], None, None, None, None, None, None)
+        return BatchContacts(R, *(given[k] for k in names), None)

@@ -51,6 +51,13 @@ allocated once, with its sync(), against run_sampled(steps, EVERY) on the
 same batch, alternating; seconds per run, and the ratio to the same steps
 unsampled.
 
+--contacts R: instead, the contact query with R records per body on a batch
+that has stepped `--steps` steps: contacts_device(R) per call (tensors
+allocated once, 20 calls and one sync() per window) against one step_async(1)
+of the same batch, and the host form contacts(R) against get_state(),
+alternating; seconds per call.  With --box-pile NX,NY,LAYERS the scene is that
+pile (the mixed-template instance of the query's kernel).
+
 Prints one JSON line and writes it to --out (default
 profiles/batch/batch_bench.json).  Needs the GPU: there is no fallback.
 """
@@ -324,6 +331,47 @@ def bench_sampled_device(rb, sc, E, steps, every, reps, dtype):
     return out
 
 
+def bench_contacts(rb, sc, E, R, settle, reps, dtype, calls=20):
+    """Seconds per call of the contact query on a batch that has stepped
+    `settle` steps: contacts_device(R) into tensors allocated once against one
+    step_async(1) (each `calls` calls and one sync() per window), and the host
+    form contacts(R) against get_state(), alternating."""
+    import torch
+    with rb.BatchWorld(sc, E, dtype=dtype) as b:
+        b.set_params(restitution=np.linspace(0.5, 1.0, E))
+        b.use_stream(torch.cuda.current_stream().cuda_stream)
+        if b.step(settle):
+            raise RuntimeError("environments failed")
+        out = b.contacts_device(max_records=R)
+        b.sync()
+        host = b.contacts(max_records=R)                # warm-up of both, and the comparison
+        same = bool(all(np.array_equal(getattr(out, f).cpu().numpy(), getattr(host, f))
+                        for f in ("counts", "partner", "kind", "dist", "pos", "frame")))
+        listed = int(np.maximum(host.counts, 0).sum())
+        q0, v0 = b.get_state()
+        t = {"contacts_device": [], "step_async_1": [], "contacts_host": [], "get_state": []}
+
+        def window(name, f, n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                f()
+            b.sync()
+            t[name].append((time.perf_counter() - t0) / n)
+
+        for _ in range(reps):
+            window("contacts_device", lambda: b.contacts_device(out=out), calls)
+            b.set_state(q0, v0)
+            window("step_async_1", lambda: b.step_async(1), calls)
+            b.set_state(q0, v0)
+            window("contacts_host", lambda: b.contacts(max_records=R), 1)
+            window("get_state", b.get_state, 1)
+    res = dict(max_records=R, settle_steps=settle, calls_per_window=calls, contacts_listed=listed,
+               truncated=host.truncated, identical=same, **{k: _summary(v) for k, v in t.items()})
+    res["device_over_step"] = res["contacts_device"]["median"] / res["step_async_1"]["median"]
+    res["host_over_get_state"] = res["contacts_host"]["median"] / res["get_state"]["median"]
+    return res
+
+
 def bench_world(rb, sc, steps, reps, dtype, law="mujoco", **kw):
     with (rb.World(sc, dtype=dtype, **kw) if law == "mujoco" else rb.World(sc, dtype=dtype, law=law)) as w:
         w.step(steps)                                   # warm-up (captures the step graph)
@@ -356,6 +404,8 @@ def main():
                     help="a closed loop's iteration of K steps through device tensors against host arrays")
     ap.add_argument("--sampled-device", type=int, default=0, metavar="EVERY",
                     help="time run_sampled_device(steps, EVERY) against run_sampled(steps, EVERY)")
+    ap.add_argument("--contacts", type=int, default=-1, metavar="R",
+                    help="time the contact query with R records per body, after --steps settling steps")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "batch_bench.json"))
     a = ap.parse_args()
 
@@ -368,7 +418,15 @@ def main():
                version=rbhip.load().rb_version().decode())
     if a.law != "mujoco":
         res["law"] = a.law
-    if a.box_pile:
+    if a.contacts >= 0:
+        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or a.sampled_device:
+            raise SystemExit("--contacts: on its own (with --box-pile for a mixed template), under the default law")
+        if a.box_pile:
+            sc = scenes.box_pile(*(int(t) for t in a.box_pile.split(",")))
+            res.update(scene=sc.name, bodies_per_env=sc.n)
+        res.update(unit="seconds per call")
+        res["contacts"] = {str(E): bench_contacts(rbhip, sc, E, a.contacts, a.steps, a.reps, a.dtype) for E in a.envs}
+    elif a.box_pile:
         if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep:
             raise SystemExit("--box-pile: the plain measurement under the default law only")
         sc = scenes.box_pile(*(int(t) for t in a.box_pile.split(",")))
