@@ -82,6 +82,9 @@ template <typename T> __device__ __forceinline__ bool col_of(T x, T inv, int32_t
     frac = f - fl;
     return true;
 }
+// the third coordinate has no column, but the same check (cell_of tests all
+// three: a non-finite or out-of-range z is RB_EDOM in every form)
+template <typename T> __device__ __forceinline__ bool height_ok(T z, T inv) { return absval(z * inv) < T(1 << 29); }
 
 // The bins a window column's records come from: along each axis the slot's
 // own bin, and for the two outer columns of each side the neighbour's (at
@@ -494,7 +497,7 @@ void tile_step_kernel(const int32_t *cur_off, int32_t ntx, int32_t nty, const ui
         // the body's column after the step, relative to its tile at the start
         int32_t cx2, cy2;
         T fr;
-        if (!col_of(x.x, p.inv_col, cx2, fr) || !col_of(x.y, p.inv_col, cy2, fr)) {
+        if (!col_of(x.x, p.inv_col, cx2, fr) || !col_of(x.y, p.inv_col, cy2, fr) || !height_ok(x.z, p.inv_col)) {
             tile_fail(p, TILE_WHY_DOMAIN);
         } else {
             ex_ = cx2 - (cx - vx);
@@ -551,7 +554,7 @@ template <typename T>
 __device__ __forceinline__ bool tile_place(const TileIO<T> &p, const Snap<T> &sn, int64_t &slot, int &e) {
     int32_t cx, cy;
     T fr;
-    if (!col_of(sn.x, p.inv_col, cx, fr) || !col_of(sn.y, p.inv_col, cy, fr)) return false;
+    if (!col_of(sn.x, p.inv_col, cx, fr) || !col_of(sn.y, p.inv_col, cy, fr) || !height_ok(sn.z, p.inv_col)) return false;
     const int32_t tx = fdiv(cx, p.tc), ty = fdiv(cy, p.tc);
     slot = (int64_t)pmod(ty, p.nty) * p.ntx + pmod(tx, p.ntx);
     e = (cy - ty * p.tc + 1) * (p.tc + 2) + (cx - tx * p.tc + 1);
