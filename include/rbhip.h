@@ -338,7 +338,9 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
 /* Many small independent scenes ("environments") stepped by one launch: a
  * parameter sweep, an ensemble of initial conditions, a domain-randomised
  * batch of the reference's scenes (1 to 4 bodies each).  A batch is n_envs
- * replicas of a template environment of M = n_bodies <= 64 bodies; the
+ * replicas of a template environment of M = n_bodies <= 64 bodies
+ * (rb_batch_create, rb_batch_create_mixed) or <= RB_BATCH_MAX_BODIES = 256
+ * bodies (rb_batch_create_wide); the
  * plane count, dt, the contact threshold and the normal convention are per
  * batch; restitution / friction / body constants / state and, additive to
  * 0.4 (rb_version is unchanged), the planes' values, gravity and applied
@@ -348,9 +350,9 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * Arrays are environment-major: body k of environment e at row e*M + k.
  * Not covered (use rb_world): contacts recorded inside a step (a batch is
  * asked for the contact list of its current state: rb_batch_contacts), sharding,
- * per-environment kinds or plane counts, more than 64 bodies per
+ * per-environment kinds or plane counts, more than 256 bodies per
  * environment; under RB_LAW_BALLS also per-environment planes, applied
- * forces and the contact query.
+ * forces, the contact query and environments of more than 64 bodies.
  * A batch handle is not thread-safe; every call that takes host arrays is
  * synchronous (the device-resident boundary below only enqueues).
  *
@@ -358,6 +360,8 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * on a shared device); longer runs are several launches, with the same
  * result however a run is cut into launches or calls. */
 #define RB_BATCH_CHUNK 256
+/* Most bodies of an environment (rb_batch_create_wide). */
+#define RB_BATCH_MAX_BODIES 256
 typedef struct rb_batch rb_batch;
 /* Replaces one MjModel/MjData pair per scene variant (as rb_world_create:
  * collision.py:56, multi_sphere_bounce.py:42).  scene: the template
@@ -377,6 +381,22 @@ int  rb_batch_create(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs)
  * rb_batch_set_contact_law(RB_LAW_BALLS) is RB_EUNSUPPORTED: that law takes
  * spheres only. */
 int  rb_batch_create_mixed(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs);
+/* rb_batch_create_mixed for a template of 1..RB_BATCH_MAX_BODIES bodies
+ * (box_pile(4, 4, 4): 70 bodies; a 16 x 16 sphere field: 256).  Additive to
+ * 0.4 (rb_version is unchanged).  Up to 64 bodies it gives exactly the batch
+ * rb_batch_create_mixed gives: same kernels, same bits.  From 65 bodies on the
+ * batch is wide: an environment is one workgroup of 2 to 4 waves instead of
+ * (a part of) one wave, every body still testing every other body of its
+ * environment in ascending id, so an environment steps bit-identically to an
+ * rb_world of its scene wherever the world's partner lists (max_partners <=
+ * 32) hold the scene; the batch itself has no partner bound.  Every other
+ * rb_batch_* call works on a wide batch as on any other, failure semantics
+ * included: a failing body freezes its whole environment, bodies in other
+ * waves too, and no other environment.  Validation and codes are
+ * rb_batch_create's (RB_EINVAL for 0 or 257 bodies).  Not covered on a wide
+ * batch: rb_batch_set_contact_law(RB_LAW_BALLS) returns RB_EUNSUPPORTED and
+ * changes nothing (the two-ball law across waves is not implemented). */
+int  rb_batch_create_wide(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs);
 void rb_batch_destroy(rb_batch *b);
 /* Per-environment restitution / friction, [n_envs] each; NULL = use the
  * scalar given to rb_batch_step.  Replaces the per-scene constants of

@@ -1,5 +1,7 @@
-// rb_api_batch.hip — batched worlds (rb_batch_*; kernels in rb_batch.hip).
-// E replicas of a template environment of M <= 64 bodies, body b of
+// rb_api_batch.hip — batched worlds (rb_batch_*; kernels in rb_batch.hip,
+// rb_batch_boxes.hip and, for an environment of more than 64 bodies,
+// rb_batch_wide.hip).
+// E replicas of a template environment of M <= 256 bodies, body b of
 // environment e at slot e * M + b of every device row.  All work is enqueued
 // on the batch's stream (its own, or the caller's: rb_batch_set_stream); the
 // entries that take host arrays return after it finished, the device-resident
@@ -14,7 +16,7 @@
 
 using namespace rb::host;
 
-static_assert(BATCH_EDOM == RB_EDOM && BATCH_CHUNK == RB_BATCH_CHUNK, "batch constants");
+static_assert(BATCH_EDOM == RB_EDOM && BATCH_CHUNK == RB_BATCH_CHUNK && BATCH_WIDE_MAX == RB_BATCH_MAX_BODIES, "batch constants");
 
 struct rb_batch {
     int dtype = RB_F64, esz = 8, device = 0;
@@ -24,6 +26,7 @@ struct rb_batch {
     int32_t M = 0, n_planes = 0, oriented = 1;
     bool box = false;                  // the template is one box
     bool mixed = false;                // a box among several bodies (rb_batch_create_mixed): batch_mixed_kernel
+    bool wide = false;                 // more than 64 bodies (rb_batch_create_wide): the kernels of rb_batch_wide.hip
     int32_t *d_kind = nullptr;         // [M] the template's kinds on the device (mixed)
     std::vector<int32_t> kind;         // [M] the template's kinds
     double planes[RB_MAX_PLANES][6] = {};
@@ -181,6 +184,7 @@ template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double
 
 // one launch of the batch's step kernel (rec: the recording instance)
 template <typename T> hipError_t batch_launch(rb_batch *b, const BatchParams<T> &p, bool rec) {
+    if (b->wide) return launch_batch_wide<T>(p, b->mixed, rec, b->stream);
     if (b->mixed) return launch_batch_mixed<T>(p, rec, b->stream);
     return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, rec, b->stream);
 }
@@ -322,12 +326,14 @@ int batch_dev_ptr(const rb_batch *b, const void *p, const char *name) {
     return RB_OK;
 }
 
-// rb_batch_create / rb_batch_create_mixed (mixed: a box among several bodies is accepted)
-int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mixed) {
+// rb_batch_create / rb_batch_create_mixed / rb_batch_create_wide (mixed: a box
+// among several bodies is accepted; max_bodies: the entry's bound on n_bodies)
+int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mixed, int max_bodies = BATCH_BLOCK) {
     if (!out || !d) return fail(RB_EINVAL, "null argument");
     *out = nullptr;
     if (n_envs < 1) return fail(RB_EINVAL, "n_envs must be >= 1");
-    if (d->n_bodies < 1 || d->n_bodies > 64) return fail(RB_EINVAL, "n_bodies (bodies per environment) must be in [1, 64]");
+    if (d->n_bodies < 1 || d->n_bodies > max_bodies)
+        return fail(RB_EINVAL, "n_bodies (bodies per environment) must be in [1, %d]", max_bodies);
     if (d->world_size != 1 || d->rank != 0) return fail(RB_EINVAL, "a batch is not sharded: world_size must be 1, rank 0");
     if (n_envs > ((int64_t)INT32_MAX / 2) / d->n_bodies) return fail(RB_EINVAL, "n_envs * n_bodies out of range");
     if (d->n_planes < 0 || d->n_planes > RB_MAX_PLANES) return fail(RB_EINVAL, "n_planes must be in [0, %d]", RB_MAX_PLANES);
@@ -358,6 +364,7 @@ int batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs, bool mi
     b->N = b->E * b->M;
     b->mixed = any_box && d->n_bodies > 1;
     b->box = any_box && !b->mixed;
+    b->wide = d->n_bodies > BATCH_BLOCK;
     b->kind.assign(d->kind, d->kind + d->n_bodies);
     b->n_planes = d->n_planes;
     for (int k = 0; k < d->n_planes; ++k)
@@ -423,7 +430,9 @@ int batch_check_contact_law(const rb_batch *b) {
 int batch_launch_contacts(rb_batch *b, const ContactQuery &q) {
     HIPCHK(by_real(b->dtype, [&](auto t) {
         using T = decltype(t);
-        return launch_batch_contacts<T>(batch_params<T>(b, 0, 1.0, 0.0, 0.0, 0.0), q, b->mixed, b->stream);
+        const BatchParams<T> p = batch_params<T>(b, 0, 1.0, 0.0, 0.0, 0.0);
+        return b->wide ? launch_batch_wide_contacts<T>(p, q, b->mixed, b->stream)
+                       : launch_batch_contacts<T>(p, q, b->mixed, b->stream);
     }));
     return RB_OK;
 }
@@ -440,6 +449,11 @@ int rb_batch_create(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
 int rb_batch_create_mixed(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
     ApiScope api_scope_(d ? d->device : -1);
     return batch_create(out, d, n_envs, true);
+}
+
+int rb_batch_create_wide(rb_batch **out, const rb_scene_desc *d, int64_t n_envs) {
+    ApiScope api_scope_(d ? d->device : -1);
+    return batch_create(out, d, n_envs, true, BATCH_WIDE_MAX);
 }
 
 void rb_batch_destroy(rb_batch *b) {
@@ -545,6 +559,9 @@ int rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol) {
     if (!(tol >= 0) || !(tol < 1e6)) return fail(RB_EINVAL, "tol must be finite and >= 0");
     if (law == RB_LAW_BALLS) {
         if (b->box || b->mixed) return fail(RB_EUNSUPPORTED, "the two-ball law takes spheres only");
+        if (b->wide)
+            return fail(RB_EUNSUPPORTED, "the two-ball law takes environments of at most %d bodies (this one has %d)",
+                        BATCH_BLOCK, b->M);
         const double ground[6] = {0, 0, 1, 0, 0, 0};
         if (b->n_planes > 1 || (b->n_planes == 1 && memcmp(b->planes[0], ground, sizeof(ground)) != 0))
             return fail(RB_EUNSUPPORTED, "the two-ball law's only plane is the z = 0 ground (ball_collision.py:88-90)");

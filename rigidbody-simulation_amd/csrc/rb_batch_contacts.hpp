@@ -31,5 +31,9 @@ struct ContactQuery {
 // (p.cs.kind: its M kinds), the instance that holds the box narrowphase.
 template <typename T>
 hipError_t launch_batch_contacts(const BatchParams<T> &p, const ContactQuery &q, bool mixed, hipStream_t s);
+// the same for an environment of more than BATCH_BLOCK bodies (rb_batch_wide.hip:
+// one row per workgroup); boxes: the template holds a box
+template <typename T>
+hipError_t launch_batch_wide_contacts(const BatchParams<T> &p, const ContactQuery &q, bool boxes, hipStream_t s);
 
 }  // namespace rb

@@ -472,7 +472,8 @@ template <typename T> hipError_t launch_kat_pair_impulse(int64_t n, const double
 // ---- batched worlds (rb_batch.hip) -----------------------------
 // E independent environments of M <= 64 bodies; body b of environment e is
 // slot e * M + b of every row.  One lane per body, one wave per workgroup,
-// floor(64 / M) whole environments per wave.
+// floor(64 / M) whole environments per wave.  (M in 65..256: one environment per
+// workgroup of 2 to 4 waves, rb_batch_wide.hip.)
 constexpr int BATCH_BLOCK = 64;          // threads per workgroup: one wave
 constexpr int BATCH_CHUNK = 256;         // most steps of one launch (RB_BATCH_CHUNK, include/rbhip.h)
 constexpr int32_t BATCH_EDOM = -33;      // RB_EDOM, as the status word records it
@@ -535,6 +536,12 @@ template <typename T> hipError_t launch_batch_step(const BatchParams<T> &p, bool
 // the same for a template that mixes spheres and boxes (rb_batch_boxes.hip:
 // batch_mixed_kernel); p.cs.kind: the template's M kinds
 template <typename T> hipError_t launch_batch_mixed(const BatchParams<T> &p, bool rec, hipStream_t s);
+// the same for an environment of BATCH_BLOCK < M <= BATCH_WIDE_MAX bodies
+// (rb_batch_wide.hip: batch_wide_kernel, one environment per workgroup of 2-4
+// waves); boxes: the template holds a box (p.cs.kind: its M kinds).  The ENVS
+// instances' dynamic LDS is n_planes * 6 reals.
+constexpr int BATCH_WIDE_MAX = 256;      // RB_BATCH_MAX_BODIES, include/rbhip.h
+template <typename T> hipError_t launch_batch_wide(const BatchParams<T> &p, bool boxes, bool rec, hipStream_t s);
 // slots [first, first + n) of the sample buffer -> the boundary's rows, in
 // double: qpos [n][E * M][7] and (rows == 13) qvel [n][E * M][6]
 template <typename T>

@@ -78,6 +78,7 @@ SIGNATURES = {
     "rb_world_stats": (C.c_int, [_P, C.POINTER(_I64), _I32]),
     "rb_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), _I64]),
     "rb_batch_create_mixed": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), _I64]),
+    "rb_batch_create_wide": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), _I64]),
     "rb_batch_destroy": (None, [_P]),
     "rb_batch_set_params": (C.c_int, [_P, _P, _P]),
     "rb_batch_set_bodies": (C.c_int, [_P, _P, _P, _P]),

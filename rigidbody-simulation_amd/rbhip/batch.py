@@ -11,7 +11,10 @@ angle of cube_incline.py, model.opt.gravity, data.xfrc_applied.  Every
 environment steps bit-identically to a World of the same scene, under the
 default contact law or the two-ball law of ball_collision.py.  A scene may
 mix spheres and boxes (scenes.box_pile: stacks of cubes), box-involved pairs
-included; from_scenes over a list of seeds is an ensemble of piles.
+included; from_scenes over a list of seeds is an ensemble of piles.  A
+scene holds up to 256 bodies: up to 64 an environment is (a part of) one
+wave, from 65 on one workgroup of 2 to 4 waves (a wide batch), with the same
+interface and the same bits; only the two-ball law stops at 64.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
 multi_sphere_logger.py), one per environment, sampled on the device.
@@ -104,9 +107,11 @@ class BatchContacts:
 class BatchWorld:
     def __init__(self, scene: Scene, n_envs: int, device: int = 0, dtype: str = "f64",
                  normal_convention: Optional[str] = None, law: str = "mujoco", tol: float = 0.01):
-        """scene: the template environment (1..64 bodies, spheres and boxes
+        """scene: the template environment (1..256 bodies, spheres and boxes
         in any mix: scenes.box_pile), replicated n_envs times with the
-        scene's initial state.
+        scene's initial state.  More than 64 bodies make a wide batch
+        (rb_batch_create_wide): everything works as on any other batch but
+        law="balls", which is refused (RbError, RB_EUNSUPPORTED).
 
         law: "mujoco" (the per-body law of collision.py /
         multi_sphere_bounce.py) or "balls" (the symmetric two-ball law of
@@ -139,6 +144,8 @@ class BatchWorld:
         # a box among several bodies: the entry point that steps box-involved pairs
         mixed = scene.n > 1 and bool(np.any(kind != 0))
         create = "rb_batch_create_mixed" if mixed else "rb_batch_create"
+        if scene.n > 64:        # an environment across several waves
+            create = "rb_batch_create_wide"
         _lib.check(getattr(L, create)(C.byref(h), C.byref(d), self.n_envs), create)
         self._h = h
         self._L = L
@@ -209,7 +216,9 @@ class BatchWorld:
         """"mujoco" or "balls" (as World.set_contact_law).  Under "balls" the
         threshold given to step() and the inertia rows of set_bodies() are
         ignored: the law derives the inverse inertia from mass and radius
-        (ball_collision.py:39-41).  The law may be switched between calls."""
+        (ball_collision.py:39-41).  The law may be switched between calls.
+        "balls" on a batch of more than 64 bodies per environment is refused
+        (RbError, RB_EUNSUPPORTED) and changes nothing."""
         code = {"mujoco": _lib.RB_LAW_MUJOCO, "balls": _lib.RB_LAW_BALLS}.get(law, law)
         if not isinstance(code, int):
             raise ValueError(f"unknown contact law {law!r}")

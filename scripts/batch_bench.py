@@ -38,6 +38,11 @@ LAYERS) (columns of cubes, some capped with a sphere: box-involved pairs, the
 mixed-template kernel) with a friction sweep (0.2 .. 0.8 over the
 environments) against one World(scene, max_partners=32).
 
+--wide-pile NX,NY,LAYERS: --box-pile for a pile of 65 to 256 bodies, which is
+a wide batch (one environment per workgroup of 2 to 4 waves), against one
+World(scene, max_partners=32), the most a world takes: box_pile(4, 4, 4) is 70
+bodies, box_pile(8, 8, 3) 214.
+
 --device-loop K: instead, a closed loop's iteration (new applied forces, K
 steps, read the state, reset 1 % of the environments) through the
 device-resident boundary (set_xfrc_device, step_async(K), get_state_device,
@@ -400,6 +405,8 @@ def main():
                     help="N cube-incline angles as one batch against N one-environment batches")
     ap.add_argument("--box-pile", default="", metavar="NX,NY,LAYERS",
                     help="scene box_pile(NX, NY, LAYERS), a friction sweep, against one World(max_partners=32)")
+    ap.add_argument("--wide-pile", default="", metavar="NX,NY,LAYERS",
+                    help="--box-pile for a pile of 65..256 bodies (a wide batch) against one World(max_partners=32)")
     ap.add_argument("--device-loop", type=int, default=0, metavar="K",
                     help="a closed loop's iteration of K steps through device tensors against host arrays")
     ap.add_argument("--sampled-device", type=int, default=0, metavar="EVERY",
@@ -426,11 +433,15 @@ def main():
             res.update(scene=sc.name, bodies_per_env=sc.n)
         res.update(unit="seconds per call")
         res["contacts"] = {str(E): bench_contacts(rbhip, sc, E, a.contacts, a.steps, a.reps, a.dtype) for E in a.envs}
-    elif a.box_pile:
-        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep:
-            raise SystemExit("--box-pile: the plain measurement under the default law only")
-        sc = scenes.box_pile(*(int(t) for t in a.box_pile.split(",")))
+    elif a.box_pile or a.wide_pile:
+        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or (a.box_pile and a.wide_pile):
+            raise SystemExit("--box-pile / --wide-pile: one of them, the plain measurement under the default law only")
+        sc = scenes.box_pile(*(int(t) for t in (a.box_pile or a.wide_pile).split(",")))
+        if a.wide_pile and not 64 < sc.n <= 256:
+            raise SystemExit(f"--wide-pile: a pile of 65..256 bodies ({sc.n} given; --box-pile takes up to 64)")
         res.update(scene=sc.name, bodies_per_env=sc.n, sweep="friction 0.2 .. 0.8")
+        if a.wide_pile:
+            res.update(pile=a.wide_pile, wide=True)
         res["world"] = bench_world(rbhip, sc, a.steps, a.reps, a.dtype, max_partners=32)
         res["batch"] = {str(E): bench_batch(rbhip, sc, E, a.steps, a.reps, a.dtype, sweep={"friction": (0.2, 0.8)})
                         for E in a.envs}
