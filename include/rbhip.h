@@ -124,6 +124,43 @@ int rb_get_state(rb_world *w, double *qpos, double *qvel);
  * (collision.py:66-67).  Host pointer, copied. */
 int rb_set_xfrc(rb_world *w, const double *xfrc);
 
+/* ---- the device-resident boundary (world_size 1) ------------------------ */
+/* The same three transfers with the caller's arrays in device memory on the
+ * world's device: qpos [N][7], qvel [N][6], xfrc [N][6], of doubles or floats
+ * (io_dtype RB_F64 | RB_F32) whatever the world's real type; conversion is a
+ * C cast.  An array may start at any element (16-byte aligned ones move 16
+ * bytes per lane).  Every call is enqueued on the world's stream
+ * (rb_set_stream) and does not wait, but for the cases named below: a caller
+ * on that stream (a controller, a force field, a renderer in torch) exchanges
+ * state and forces with the world without a copy across PCIe and without a
+ * host synchronisation; rb_sync waits.  Replaces, for such a caller, the host
+ * round trip of data.qpos / data.qvel / data.xfrc_applied
+ * (multi_sphere_bounce.py:50-51, :85-88; collision.py:66-67).
+ * All three return RB_EINVAL for a null world, a null array or an unknown
+ * io_dtype and RB_EUNSUPPORTED for a world with world_size > 1 (a shard's
+ * boundary is rb_gpos_buffer), before any device call.
+ *   rb_get_state_dev: writes qpos and qvel; either may be NULL, not both.
+ *     Like every reader of the state it first runs the check of a run that
+ *     awaits one: after steps in the tile form it waits for that run.  Under
+ *     RB_LAW_BALLS the positions are the state's own (as rb_get_state).
+ *   rb_set_state_dev: rb_set_state from device memory, with its bookkeeping
+ *     (the next step rebuilds the broadphase table; a later rb_set_state is
+ *     never skipped as unchanged).  refit != 0: the broadphase layout is then
+ *     fitted to the new positions, as rb_set_state fits it to the host copy,
+ *     through one read-back of the positions: it waits, and is meant for a
+ *     new scene.  refit == 0: the layout stays and the call is enqueued only,
+ *     for resets inside the extent the world was fitted for.  The layout
+ *     decides speed, never bits, and a synchronous rb_step still refits when
+ *     a bucket overflows.
+ *   rb_set_xfrc_dev: rb_set_xfrc from device memory.  The first call after
+ *     "no forces" allocates the force rows and drops the captured graphs as
+ *     rb_set_xfrc does (it waits); later calls are enqueued only, ordered
+ *     after the steps in flight.  rb_set_xfrc(w, NULL) clears the forces. */
+int rb_get_state_dev(rb_world *w, void *qpos, void *qvel, int32_t io_dtype);
+int rb_set_state_dev(rb_world *w, const void *qpos, const void *qvel,
+                     int32_t io_dtype, int32_t refit);
+int rb_set_xfrc_dev(rb_world *w, const void *xfrc, int32_t io_dtype);
+
 /* ---- the hot path ------------------------------------------------------ */
 /* nsteps reference steps: contact generation (mj_forward's role,
  * collision.py:57), gravity (collision.py:66-70), the per-contact

@@ -366,13 +366,14 @@ int snapshot_to_host(rb_world *w, std::vector<double> &rows) {
     });
 }
 
-// the layout period refitted to the current positions (the snapshot)
-static int refit_from_device(rb_world *w) {
+// the layout period refitted to the current positions (the snapshot, read
+// back once: waits for the stream); force: fit_period's
+int refit_from_device(rb_world *w, bool force) {
     std::vector<double> sn, q((size_t)7 * w->N, 0.0);
     WCHK(snapshot_to_host(w, sn));
     for (int64_t b = 0; b < w->N; ++b)
         for (int d = 0; d < 3; ++d) q[(size_t)(7 * b + d)] = sn[(size_t)(4 * b + d)];
-    fit_period(w, q.data(), true);
+    fit_period(w, q.data(), force);
     return RB_OK;
 }
 // ---- captured step graphs ---------------------------------------------------

@@ -2,73 +2,18 @@
 // the caller's arrays of structures <-> the batch's struct-of-arrays rows, both
 // in device memory.  With no PCIe copy behind them these transposes are the
 // whole cost of a closed loop's iteration, so both sides are moved as
-// contiguous runs:
-//
-// A block of SPAN threads takes SPAN consecutive rows (body slots).  Their
-// SPAN x 7 (qpos) or SPAN x 6 (qvel, xfrc) elements are one flat run of the
-// caller's array, moved with consecutive lanes on consecutive words: 16 bytes
-// per lane when the run's base is 16-byte aligned (VEC), else one element per
-// lane (a view may start at any element).  The run passes through a tile in
-// LDS with PITCH = 7 elements between rows, for both widths: lane t then reads
-// or writes its row at element 7 t + d, an odd stride in elements, which
-// spreads a lane group over all banks for 4- and 8-byte elements alike (the
-// natural stride 6 would be 2-way conflicted).  The rows of the batch are read
-// or written one lane per slot, contiguously per row.
+// contiguous runs through a tile in LDS (rb_dev_span.hpp): a block of SPAN
+// threads takes SPAN consecutive rows (body slots); the rows of the batch are
+// read or written one lane per slot, contiguously per row.
 #include <math.h>
 
 #include <algorithm>
 
 #include "rb_batch_dev.hpp"
+#include "rb_dev_span.hpp"
 
 namespace rb {
 namespace {
-
-constexpr int SPAN = 256;              // rows of a block, and its threads
-constexpr int PITCH = 7;               // elements between two rows of a tile
-
-// the tile element of element f of a flat run of rows of W elements
-template <int W> __device__ __forceinline__ int tile_at(int f) { return W == PITCH ? f : f + f / W; }
-
-template <typename IO, bool VEC> struct Run {
-    static constexpr int V = VEC ? 16 / (int)sizeof(IO) : 1;       // elements per lane and access
-    struct alignas(V * sizeof(IO)) Vec { IO v[V]; };
-};
-
-// n elements from src (rows of W) into the tile; MASKED: only the rows with row_on set are read
-template <typename IO, int W, bool VEC, bool MASKED>
-__device__ __forceinline__ void span_load(const IO *src, int n, IO *tile, const uint8_t *row_on) {
-    using R = Run<IO, VEC>;
-    const int nv = n / R::V;
-    for (int i = threadIdx.x; i < nv; i += SPAN) {
-        const int f = i * R::V;
-        const bool first = !MASKED || row_on[f / W], last = !MASKED || row_on[(f + R::V - 1) / W];
-        if (first && last) {
-            const typename R::Vec x = *reinterpret_cast<const typename R::Vec *>(src + f);
-#pragma unroll
-            for (int j = 0; j < R::V; ++j) tile[tile_at<W>(f + j)] = x.v[j];
-        } else if (first || last) {          // an access across the edge of the mask: by element
-            for (int j = 0; j < R::V; ++j)
-                if (row_on[(f + j) / W]) tile[tile_at<W>(f + j)] = src[f + j];
-        }
-    }
-    for (int f = nv * R::V + threadIdx.x; f < n; f += SPAN)     // (the batch's last span only)
-        if (!MASKED || row_on[f / W]) tile[tile_at<W>(f)] = src[f];
-}
-
-template <typename IO, int W, bool VEC> __device__ __forceinline__ void span_store(IO *dst, int n, const IO *tile) {
-    using R = Run<IO, VEC>;
-    const int nv = n / R::V;
-    for (int i = threadIdx.x; i < nv; i += SPAN) {
-        const int f = i * R::V;
-        typename R::Vec x;
-#pragma unroll
-        for (int j = 0; j < R::V; ++j) x.v[j] = tile[tile_at<W>(f + j)];
-        *reinterpret_cast<typename R::Vec *>(dst + f) = x;
-    }
-    for (int f = nv * R::V + threadIdx.x; f < n; f += SPAN) dst[f] = tile[tile_at<W>(f)];
-}
-
-__device__ __forceinline__ int span_rows(int64_t N, int64_t row0) { return (int)(N - row0 < SPAN ? N - row0 : SPAN); }
 
 template <typename T, typename IO, bool VEC, bool MASKED>
 __global__ __launch_bounds__(SPAN) void dev_state_in_kernel(DevState<T> p, const uint8_t *mask, const IO *qpos,
@@ -193,13 +138,6 @@ __global__ __launch_bounds__(SPAN) void dev_samples_out_kernel(const T *samp, in
     __syncthreads();
     span_store<IO, 7, VEC>(qpos + (k * N + row0) * 7, rows * 7, s_q);
     if (vel) span_store<IO, 6, VEC>(qvel + (k * N + row0) * 6, rows * 6, s_v);
-}
-
-unsigned spans(int64_t N) { return (unsigned)((N + SPAN - 1) / SPAN); }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-template <typename F> void as_flag(bool flag, F &&f) {
-    if (flag) f(std::true_type{});
-    else f(std::false_type{});
 }
 
 }  // namespace

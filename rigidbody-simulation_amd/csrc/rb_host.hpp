@@ -295,6 +295,7 @@ int graph_replay(rb_world *w, int64_t K, int variant, double dt, double e, doubl
                  const std::function<int(hipStream_t, int64_t)> &seq);
 int gen_guard(rb_world *w, int64_t nsteps);
 int snapshot_to_host(rb_world *w, std::vector<double> &rows);
+int refit_from_device(rb_world *w, bool force = true);
 int enqueue_steps(rb_world *w, int64_t nsteps, double dt, double e, double mu, double thr, bool sharded = false);
 
 // ---- rb_api_tiles.hip --------------------------------------------------------

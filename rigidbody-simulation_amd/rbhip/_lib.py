@@ -51,6 +51,9 @@ SIGNATURES = {
     "rb_set_state": (C.c_int, [_P, _P, _P]),
     "rb_get_state": (C.c_int, [_P, _P, _P]),
     "rb_set_xfrc": (C.c_int, [_P, _P]),
+    "rb_get_state_dev": (C.c_int, [_P, _P, _P, _I32]),
+    "rb_set_state_dev": (C.c_int, [_P, _P, _P, _I32, _I32]),
+    "rb_set_xfrc_dev": (C.c_int, [_P, _P, _I32]),
     "rb_step": (C.c_int, [_P, _I64, _D, _D, _D, _D]),
     "rb_step_async": (C.c_int, [_P, _I64, _D, _D, _D, _D]),
     "rb_sync": (C.c_int, [_P]),

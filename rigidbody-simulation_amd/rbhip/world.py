@@ -13,6 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._devarray import _IO_CODES, _device_array, _new_tensor, _pair_typestr
 from .scenes import Scene
 
 COMM_ID_BYTES = 128      # ncclUniqueId (rccl.h NCCL_UNIQUE_ID_BYTES)
@@ -27,7 +28,7 @@ class World:
         ball_collision.py:73-125 (tol: its contact tolerance, :102)."""
         L = _lib.load()
         self.scene = scene
-        self.dtype = dtype
+        self.dtype, self.device = dtype, device
         self.rank, self.world_size = rank, world_size
         nc = normal_convention or scene.normal_convention
         self._kind = np.ascontiguousarray(scene.kind, np.int32)
@@ -117,6 +118,80 @@ class World:
         """Enqueue all later work on this hipStream_t (0 = HIP's null stream,
         which is torch's default stream)."""
         _lib.check(self._L.rb_set_stream(self._h, C.c_void_p(stream_handle or None)), "rb_set_stream")
+
+    # ---- the device-resident boundary ---------------------------------------
+    # Arrays are objects with __cuda_array_interface__ on the world's device
+    # (torch tensors), float64 or float32 whatever the world's dtype (converted
+    # by a cast).  Every call is enqueued on the world's stream (set_stream)
+    # and returns without waiting, but for the cases each docstring names;
+    # sync() waits.  One rank only (a shard's boundary is gpos_buffer()).
+    def get_state_device(self, out_qpos=None, out_qvel=None, dtype=None):
+        """(qpos (N, 7), qvel (N, 6)) written into out_qpos / out_qvel, or
+        into new torch tensors of `dtype` ("f64" / "f32"; None: the world's),
+        valid on the world's stream.  After a run in the tile form it waits
+        for that run's check, like every reader of the state."""
+        n = self.scene.n
+        ts = _pair_typestr(self.dtype, ("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
+        q = _new_tensor((n, 7), ts, self.device) if out_qpos is None else out_qpos
+        v = _new_tensor((n, 6), ts, self.device) if out_qvel is None else out_qvel
+        qp, _ = _device_array("out_qpos", q, (n, 7), (ts,), out=True)
+        vp, _ = _device_array("out_qvel", v, (n, 6), (ts,), out=True)
+        _lib.check(self._L.rb_get_state_dev(self._h, qp, vp, _IO_CODES[ts]), "rb_get_state_dev")
+        return q, v
+
+    def set_state_device(self, qpos, qvel, refit=True):
+        """set_state() from device arrays qpos (N, 7), qvel (N, 6) of one
+        element type.  refit=True fits the broadphase layout to the new
+        positions as set_state() does, through one read-back of the positions
+        (it waits: for a new scene); refit=False keeps the layout and only
+        enqueues (a reset inside the extent the world was fitted for).  The
+        layout decides speed, never bits."""
+        n = self.scene.n
+        ts = _pair_typestr(self.dtype, ("qpos", "qvel"), (qpos, qvel), None)
+        q, _ = _device_array("qpos", qpos, (n, 7), (ts,))
+        v, _ = _device_array("qvel", qvel, (n, 6), (ts,))
+        _lib.check(self._L.rb_set_state_dev(self._h, q, v, _IO_CODES[ts], 1 if refit else 0), "rb_set_state_dev")
+
+    def set_xfrc_device(self, xfrc):
+        """set_xfrc() from a device array (N, 6).  The first call after "no
+        forces" allocates the force rows (as set_xfrc does); later calls only
+        enqueue.  set_xfrc(None) clears the forces."""
+        ts = _pair_typestr(self.dtype, ("xfrc",), (xfrc,), None)
+        x, _ = _device_array("xfrc", xfrc, (self.scene.n, 6), (ts,))
+        _lib.check(self._L.rb_set_xfrc_dev(self._h, x, _IO_CODES[ts]), "rb_set_xfrc_dev")
+
+    def run_sampled_device(self, nsteps: int, every: int, velocities: bool = True, out_qpos=None, out_qvel=None,
+                           dtype=None, dt=None, restitution=None, friction=None, threshold=None):
+        """nsteps steps, the state sampled after every `every` of them into
+        device memory: returns (qpos (S, N, 7), qvel (S, N, 6) or None),
+        S = nsteps // every, written into out_qpos / out_qvel or new torch
+        tensors of `dtype`.  Sample s is what step(every) + get_state() returns
+        at that point; the steps left over are taken at the end.  A
+        composition of step_async() and get_state_device(): nothing waits
+        (but a tile-form run's check, as in get_state_device)."""
+        nsteps, every = int(nsteps), int(every)
+        if every < 1 or nsteps < 0:
+            raise ValueError(f"nsteps {nsteps}, every {every}: expected nsteps >= 0 and every >= 1")
+        if not velocities and out_qvel is not None:
+            raise ValueError("out_qvel: given with velocities=False")
+        S, n = nsteps // every, self.scene.n
+        ts = _pair_typestr(self.dtype, ("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
+        q = _new_tensor((S, n, 7), ts, self.device) if out_qpos is None else out_qpos
+        v = None if not velocities else _new_tensor((S, n, 6), ts, self.device) if out_qvel is None else out_qvel
+        qp, _ = _device_array("out_qpos", q, (S, n, 7), (ts,), out=True)
+        vp = None if v is None else _device_array("out_qvel", v, (S, n, 6), (ts,), out=True)[0]
+        if S > 0 and n > 0 and (qp is None or (v is not None and vp is None)):
+            raise ValueError("out_qpos / out_qvel: null device pointer")
+        p = self._params(dt, restitution, friction, threshold)
+        esz = 8 if ts == "<f8" else 4
+        for s in range(S):
+            _lib.check(self._L.rb_step_async(self._h, every, *p), "rb_step_async")
+            qs = C.c_void_p(qp.value + s * n * 7 * esz)
+            vs = None if vp is None else C.c_void_p(vp.value + s * n * 6 * esz)
+            _lib.check(self._L.rb_get_state_dev(self._h, qs, vs, _IO_CODES[ts]), "rb_get_state_dev")
+        if nsteps - S * every:
+            _lib.check(self._L.rb_step_async(self._h, nsteps - S * every, *p), "rb_step_async")
+        return q, v
 
     # ---- stepping -----------------------------------------------------------
     def _params(self, dt, restitution, friction, threshold):
