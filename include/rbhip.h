@@ -161,6 +161,69 @@ int rb_set_state_dev(rb_world *w, const void *qpos, const void *qvel,
                      int32_t io_dtype, int32_t refit);
 int rb_set_xfrc_dev(rb_world *w, const void *xfrc, int32_t io_dtype);
 
+/* ---- the contact query of a world (additive to librbhip 0.4) ----------------
+ * For the world's current state, the contact list of the bodies [first,
+ * first + count) exactly as rb_batch_contacts (below) defines it for one
+ * environment: what the reference reads as data.contact[i].dist / pos / frame
+ * / geom1 / geom2 after mj_forward (collision.py:57, :72-76), without a step.
+ * Every generated contact is listed (the step's skip rules, dist < 0 and the
+ * threshold, are not applied), in the canonical per-body order of
+ * rb_get_contacts: the planes in plane order, a box's corners in bit order
+ * with at most 4 per plane, then the partners by ascending body id, a box
+ * pair's points in generation order.  frame is the raw normal from geom1 to
+ * geom2 (no normal convention applied); geom1 is the plane of a plane contact,
+ * the lower id of two spheres or two boxes, the sphere of a sphere-box pair.
+ *
+ * Layout: dense, R = max_records slots per body.  counts [count]; partner,
+ * kind and dist [count][R]; pos and frame [count][R][3].  counts[k] is the
+ * true number of contacts of body first + k, also past R (the first R records
+ * are kept); partner is a global body id or -1 - plane.  Slots at or past the
+ * count hold kind -1 and zeros elsewhere, so every word of the output is
+ * defined.  pos and frame may be NULL, singly or together; partner, kind and
+ * dist only all together, with max_records 0: a counts-only query, for sizing.
+ *
+ * A body whose list cannot be built has counts[k] == -2 and unused slots
+ * only: one with more than 32 partners in reach (the query searches with a
+ * partner list of 32 whatever the world's max_partners), one with a
+ * non-finite or out-of-range position, and every body of the call if the
+ * query's own broadphase table overflowed.  The host form then returns
+ * RB_EOVERFLOW (RB_EDOM for the position case) with a message naming the
+ * lowest such body, all arrays written; the device form reports through
+ * counts alone.  Neither sets any sticky state, neither touches the world's
+ * error word.
+ *
+ * The query is pure: it steps nothing and changes nothing a step can see
+ * (state, broadphase tables and generations, captured graphs, the layout fit,
+ * rb_world_stats, the rb_set_state mirror, recorded contacts).  A run of steps
+ * gives the same bits and stats with any number of queries between its calls.
+ * It searches a broadphase table of its own, allocated at the first query and
+ * filled from the current positions by every call.
+ *
+ * RB_EINVAL, nothing enqueued or changed: a null world or counts;
+ * max_records < 0; max_records 0 with a record array given, or > 0 without;
+ * first < 0, count < 0 or first + count > n_bodies; in the device form an
+ * unknown io_dtype, a host pointer or memory of another device.  count 0 is
+ * RB_OK.  RB_EUNSUPPORTED before any device call: world_size > 1; RB_LAW_BALLS
+ * (that law has no contact list); the device form under a stream capture.
+ *
+ * rb_query_contacts: host arrays, synchronous; like rb_get_state it finishes
+ * the world's pending work first.  *n_truncated (may be NULL) = the listed
+ * bodies with count > max_records.  The lists are staged in a device buffer
+ * owned by the world, allocated on first use and freed with it, of at most
+ * RBHIP_CONTACT_STAGE_BYTES bytes (read at rb_world_create; default 256 MiB);
+ * a request that does not fit is cut into launches over sub-ranges (RB_EINVAL
+ * if one body's slots alone do not fit).
+ * rb_query_contacts_dev: the arrays are device memory on the world's device;
+ * dist, pos and frame of io_dtype (RB_F64 | RB_F32), converted by a C cast.
+ * Enqueued on the world's stream without waiting, but that like every reader
+ * of the state it first runs the check of a tile-form run that awaits one. */
+int rb_query_contacts(rb_world *w, int64_t first, int64_t count, int32_t max_records,
+                      int32_t *counts, int32_t *partner, int32_t *kind,
+                      double *dist, double *pos, double *frame, int64_t *n_truncated);
+int rb_query_contacts_dev(rb_world *w, int64_t first, int64_t count, int32_t max_records,
+                          int32_t *counts, int32_t *partner, int32_t *kind,
+                          void *dist, void *pos, void *frame, int32_t io_dtype);
+
 /* ---- the hot path ------------------------------------------------------ */
 /* nsteps reference steps: contact generation (mj_forward's role,
  * collision.py:57), gravity (collision.py:66-70), the per-contact

@@ -1,0 +1,250 @@
+// rb_api_contacts.hip — the contact query of a world: rb_query_contacts (host
+// arrays, synchronous) and rb_query_contacts_dev (device arrays, enqueued).
+// Kernels: rb_world_contacts.hip, and the insert kernel of rb_io.hip.
+//
+// The query owns a broadphase table (bucket lines, spill lines, a generation
+// word and an error word): allocated at the first query, freed with the world.
+// Every call bumps the table's generation, inserts every body of the current
+// snapshot into it and runs the query kernel over it.  It uses the world's
+// grid (cell size, bucket count, layout) as it stands at the call, and never
+// the tables the steps use: after rb_set_state those are stale, and inside an
+// append epoch they are not a plain table.  Nothing here changes a field of
+// the world that a step, a graph, the stats or the boundary reads: the fields
+// written are the cq_* ones alone.
+#include "rb_host.hpp"
+#include "rb_world_contacts.hpp"
+
+namespace rb::host {
+
+// the arguments both forms share, before any device call
+static int query_check(const rb_world *w, int64_t first, int64_t count, int32_t R, const void *counts, const void *partner,
+                       const void *kind, const void *dist, const void *pos, const void *frame) {
+    if (!w) return fail(RB_EINVAL, "null world");
+    if (!counts) return fail(RB_EINVAL, "counts NULL");
+    if (R < 0) return fail(RB_EINVAL, "max_records < 0");
+    const int given = (partner != nullptr) + (kind != nullptr) + (dist != nullptr);
+    if (given != 0 && given != 3) return fail(RB_EINVAL, "partner, kind and dist may be NULL only all together");
+    if (R == 0 && (given || pos || frame)) return fail(RB_EINVAL, "max_records 0 with record arrays given");
+    if (R > 0 && !given)
+        return fail(RB_EINVAL, "max_records %d with partner, kind and dist NULL (a counts-only query has max_records 0)", R);
+    if (first < 0 || count < 0 || first > w->N || count > w->N - first)
+        return fail(RB_EINVAL, "bodies [%lld, %lld + %lld) outside [0, %lld)", (long long)first, (long long)first,
+                    (long long)count, (long long)w->N);
+    return RB_OK;
+}
+static int query_supported(const rb_world *w) {
+    if (w->P > 1) return fail(RB_EUNSUPPORTED, "the contact query is for world_size 1");
+    if (w->law == RB_LAW_BALLS)
+        return fail(RB_EUNSUPPORTED, "the two-ball law has no contact list (its hit test carries a tolerance of its own)");
+    return RB_OK;
+}
+
+// the layout word without the period's split: refits move the split only, and
+// what is left decides where a bucket's header lies in the lines
+static int32_t layout_key(const rb_world *w) { return w->group & ~(0xfff << 12); }
+
+// The query's table for the world's grid as it stands.  A table of another
+// size or line layout is dropped (table growth): headers of the old layout
+// would be read as ids, and ids as headers.
+static int query_table(rb_world *w) {
+    const size_t lines = sizeof(uint32_t) * LINE_WORDS * (size_t)w->H, spill = sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES;
+    if (w->cq_line && (w->cq_H != w->H || w->cq_layout != layout_key(w))) {
+        HIPCHK(hipStreamSynchronize(w->stream));     // (a query in flight reads it)
+        HIPCHK(hipFree(w->cq_line));
+        w->cq_line = nullptr;
+    }
+    if (!w->cq_line) {
+        HIPCHK(hipMalloc((void **)&w->cq_line, lines));
+        w->cq_H = w->H;
+        w->cq_layout = layout_key(w);
+        w->cq_gen = 0;
+    }
+    if (!w->cq_spill) HIPCHK(hipMalloc((void **)&w->cq_spill, spill));
+    if (!w->cq_words) HIPCHK(hipMalloc((void **)&w->cq_words, sizeof(uint32_t) * 2));
+    // headers of generation 0 are empty buckets: a new table, and one whose
+    // generations are used up, starts from zeros
+    if (w->cq_gen == 0 || w->cq_gen == UINT32_MAX) {
+        HIPCHK(hipMemsetAsync(w->cq_line, 0, lines, w->stream));
+        HIPCHK(hipMemsetAsync(w->cq_spill, 0, spill, w->stream));
+        w->cq_gen = 0;
+    }
+    return RB_OK;
+}
+
+// what the kernels of one call read: sp.cur is the query's table
+template <typename T> static WorldContactQuery<T> make_query(const rb_world *w) {
+    WorldContactQuery<T> q{};
+    StepParams<T> &p = q.sp;
+    p.snap_cur = dp<Snap<T>>(w->snap[w->sp()], 0);
+    p.st = BodyState<T>{dp<T>(w->state, 0), w->S};
+    p.cs = BodyConsts<T>{dp<T>(w->consts, 0), w->Npad, w->kind};
+    p.n_local = w->n_local;
+    p.n_global = w->N;
+    p.S = (int32_t)w->S;
+    p.n_planes = w->n_planes;
+    for (int k = 0; k < w->n_planes; ++k)
+        for (int d = 0; d < 3; ++d) { p.pn[k][d] = (T)w->planes[k][d]; p.pp[k][d] = (T)w->planes[k][3 + d]; }
+    p.grid.inv_cs = (T)w->inv_cs;
+    p.grid.hmask = (uint32_t)(w->H - 1);
+    p.grid.H = (int32_t)w->H;
+    p.grid.super = w->group;
+    p.cur = Table<T>{w->cq_line, nullptr, w->cq_words, w->cq_spill};
+    p.err = reinterpret_cast<int32_t *>(w->cq_words + 1);
+    return q;
+}
+
+// a call's first part: the next generation, a clean error word, every body
+// of the current snapshot into the table
+static int query_fill(rb_world *w) {
+    WCHK(query_table(w));
+    w->cq_gen += 1;
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)w->cq_words, (int)w->cq_gen, 1, w->stream));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(w->cq_words + 1), 0, 1, w->stream));
+    HIPCHK(by_real(w->dtype, [&](auto t) {
+        using T = decltype(t);
+        const WorldContactQuery<T> q = make_query<T>(w);
+        InsertParams<T> ip{};
+        ip.snap = q.sp.snap_cur;
+        ip.kind = w->kind;
+        ip.first = 0;
+        ip.count = w->N;
+        ip.grid = q.sp.grid;
+        ip.tab = q.sp.cur;
+        ip.err = q.sp.err;
+        return launch_insert<T>(ip, w->stream);
+    }));
+    return RB_OK;
+}
+
+// bodies [first, first + count) into the given arrays (device memory)
+static int query_launch(rb_world *w, int64_t first, int64_t count, int32_t R, int32_t *counts, int32_t *partner,
+                        int32_t *kind, void *dist, void *pos, void *frame, bool io32) {
+    HIPCHK(by_real(w->dtype, [&](auto t) {
+        using T = decltype(t);
+        WorldContactQuery<T> q = make_query<T>(w);
+        q.counts = counts; q.partner = partner; q.kind = kind;
+        q.dist = dist; q.pos = pos; q.frame = frame;
+        q.first = first; q.count = count;
+        q.R = R;
+        q.io32 = io32;
+        return launch_world_contacts<T>(q, w->boxes, w->stream);
+    }));
+    return RB_OK;
+}
+
+static int query_dev_ptr(const rb_world *w, const void *p, const char *name) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(RB_EINVAL, "%s is not device memory (a host pointer?)", name);
+    }
+    if (a.device != w->device) return fail(RB_EINVAL, "%s is memory of device %d, the world is on device %d", name, a.device, w->device);
+    return RB_OK;
+}
+
+// The staging of the host form: a device buffer and its pinned twin, grown
+// on demand up to the world's bound.  Per body: the reals first (so every
+// array of a sub-range starts aligned), then the words.
+static size_t stage_per_body(int32_t R, bool pos, bool frame) {
+    return sizeof(double) * (size_t)R * (1 + (pos ? 3 : 0) + (frame ? 3 : 0)) + sizeof(int32_t) * (1 + 2 * (size_t)R);
+}
+static int stage_reserve(rb_world *w, size_t bytes) {
+    if (bytes <= w->cq_stage_bytes) return RB_OK;
+    HIPCHK(hipStreamSynchronize(w->stream));
+    if (w->cq_stage) { HIPCHK(hipFree(w->cq_stage)); w->cq_stage = nullptr; }
+    if (w->cq_stage_h) { HIPCHK(hipHostFree(w->cq_stage_h)); w->cq_stage_h = nullptr; }
+    w->cq_stage_bytes = 0;
+    HIPCHK(hipMalloc((void **)&w->cq_stage, bytes));
+    HIPCHK(hipHostMalloc((void **)&w->cq_stage_h, bytes, hipHostMallocDefault));
+    w->cq_stage_bytes = bytes;
+    return RB_OK;
+}
+
+}  // namespace rb::host
+
+using namespace rb::host;
+
+extern "C" {
+
+int rb_query_contacts(rb_world *w, int64_t first, int64_t count, int32_t max_records, int32_t *counts, int32_t *partner,
+                      int32_t *kind, double *dist, double *pos, double *frame, int64_t *n_truncated) {
+    ApiScope api_scope_(w ? w->device : -1);
+    const int32_t R = max_records;
+    WCHK(query_check(w, first, count, R, counts, partner, kind, dist, pos, frame));
+    WCHK(query_supported(w));
+    if (n_truncated) *n_truncated = 0;
+    if (count == 0) return RB_OK;
+    const size_t per = stage_per_body(R, pos, frame);
+    if (per > w->cq_limit)
+        return fail(RB_EINVAL, "the contact list of one body (%zu bytes) does not fit the staging buffer (%zu bytes: "
+                               "RBHIP_CONTACT_STAGE_BYTES)", per, w->cq_limit);
+    const int64_t fit = std::min<int64_t>(count, (int64_t)(w->cq_limit / per));
+    HIPCHK(hipSetDevice(w->device));
+    if (int rc = finish_pending(w)) return rc;
+    WCHK(stage_reserve(w, per * (size_t)fit));
+    WCHK(query_fill(w));
+    // a sub-range of the bodies per launch: one DMA per array into the pinned
+    // twin, then out to the caller
+    for (int64_t at0 = 0; at0 < count; at0 += fit) {
+        const size_t c = (size_t)std::min<int64_t>(fit, count - at0), cR = c * (size_t)R, at = (size_t)at0;
+        const size_t o_dist = 0, o_pos = o_dist + sizeof(double) * cR, o_frame = o_pos + (pos ? sizeof(double) * 3 * cR : 0);
+        const size_t o_counts = o_frame + (frame ? sizeof(double) * 3 * cR : 0), o_partner = o_counts + sizeof(int32_t) * c;
+        const size_t o_kind = o_partner + sizeof(int32_t) * cR;
+        char *d = w->cq_stage, *h = w->cq_stage_h;
+        WCHK(query_launch(w, first + at0, (int64_t)c, R, (int32_t *)(d + o_counts), R > 0 ? (int32_t *)(d + o_partner) : nullptr,
+                          R > 0 ? (int32_t *)(d + o_kind) : nullptr, R > 0 ? d + o_dist : nullptr, pos ? d + o_pos : nullptr,
+                          frame ? d + o_frame : nullptr, false));
+        struct Move { void *dst; size_t off, bytes; };
+        const Move moves[] = {{counts + at, o_counts, sizeof(int32_t) * c},
+                              {partner ? partner + at * R : nullptr, o_partner, sizeof(int32_t) * cR},
+                              {kind ? kind + at * R : nullptr, o_kind, sizeof(int32_t) * cR},
+                              {dist ? dist + at * R : nullptr, o_dist, sizeof(double) * cR},
+                              {pos ? pos + 3 * at * R : nullptr, o_pos, sizeof(double) * 3 * cR},
+                              {frame ? frame + 3 * at * R : nullptr, o_frame, sizeof(double) * 3 * cR}};
+        for (const Move &m : moves)
+            if (m.dst && m.bytes) HIPCHK(hipMemcpyAsync(h + m.off, d + m.off, m.bytes, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));     // (the next sub-range reuses the staging)
+        for (const Move &m : moves)
+            if (m.dst && m.bytes) memcpy(m.dst, h + m.off, m.bytes);
+    }
+    int64_t trunc = 0, bad = -1;
+    for (int64_t k = 0; k < count; ++k) {
+        trunc += counts[k] > R;
+        if (counts[k] == QUERY_NO_LIST && bad < 0) bad = k;
+    }
+    if (n_truncated) *n_truncated = trunc;
+    if (bad >= 0) {
+        int32_t bits = 0;
+        WCHK(wget(w, &bits, w->cq_words + 1, sizeof bits));
+        if (bits & ERR_BUCKET_OVERFLOW)
+            return fail(RB_EOVERFLOW, "contact query: its broadphase table overflowed; no body has a list (first: body %lld)",
+                        (long long)(first + bad));
+        if (bits & ERR_PARTNER_OVERFLOW)
+            return fail(RB_EOVERFLOW, "contact query: body %lld has more than %d partners in reach (or no valid position): no list",
+                        (long long)(first + bad), QUERY_MAXP);
+        return fail(RB_EDOM, "contact query: body %lld has a non-finite or out-of-range position: no list", (long long)(first + bad));
+    }
+    return RB_OK;
+}
+
+int rb_query_contacts_dev(rb_world *w, int64_t first, int64_t count, int32_t max_records, int32_t *counts, int32_t *partner,
+                          int32_t *kind, void *dist, void *pos, void *frame, int32_t io_dtype) {
+    ApiScope api_scope_(w ? w->device : -1);
+    WCHK(query_check(w, first, count, max_records, counts, partner, kind, dist, pos, frame));
+    if (io_dtype != RB_F64 && io_dtype != RB_F32) return fail(RB_EINVAL, "io_dtype %d is neither RB_F64 nor RB_F32", io_dtype);
+    WCHK(query_supported(w));
+    if (count == 0) return RB_OK;
+    HIPCHK(hipSetDevice(w->device));
+    const std::pair<const void *, const char *> arrays[] = {{counts, "counts"}, {partner, "partner"}, {kind, "kind"},
+                                                            {dist, "dist"},     {pos, "pos"},         {frame, "frame"}};
+    for (const auto &a : arrays)
+        if (a.first) WCHK(query_dev_ptr(w, a.first, a.second));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(w->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(RB_EUNSUPPORTED, "the contact query is not supported under a stream capture");
+    if (int rc = finish_pending(w)) return rc;
+    WCHK(query_fill(w));
+    return query_launch(w, first, count, max_records, counts, partner, kind, dist, pos, frame, io_dtype == RB_F32);
+}
+
+}  // extern "C"

@@ -90,10 +90,11 @@ void free_world(rb_world *w) {
         if (e) (void)hipEventDestroy(e);
     void *bufs[] = {w->snap[0], w->snap[1], w->qsnap[0], w->qsnap[1], w->defer_q, w->defer_cnt, w->state, w->consts, w->kind, w->xfrc, w->lead_blk, w->ep_mem,
                     w->ids[0], w->ids[1], w->spill[0], w->spill[1], w->pos[0], w->pos[1], w->plist, w->plist_cnt, w->vel[0], w->vel[1], w->err, w->rec_count, w->rec_partner, w->rec_kind,
-                    w->rec_dist};
+                    w->rec_dist, w->cq_line, w->cq_spill, w->cq_words, w->cq_stage};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (w->err_host) (void)hipHostFree(w->err_host);
+    if (w->cq_stage_h) (void)hipHostFree(w->cq_stage_h);
     if (w->own_stream) (void)hipStreamDestroy(w->own_stream);
     if (w->cap_stream) (void)hipStreamDestroy(w->cap_stream);
     delete w;
@@ -177,6 +178,9 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     if (const char *ev = getenv("RBHIP_BOX_OPTIMISTIC")) w->box_opt = atoi(ev) != 0;
     if (const char *ev = getenv("RBHIP_DIAG_OVERFLOW")) w->diag_overflow = atoi(ev);
     if (const char *ev = getenv("RBHIP_TABLE_EPOCH")) w->epoch_max = std::max(1, std::min(EPOCH_MAX, atoi(ev)));
+    // rb_query_contacts: the bound of its staging buffer
+    if (const char *ev = getenv("RBHIP_CONTACT_STAGE_BYTES"))
+        if (atoll(ev) > 0) w->cq_limit = (size_t)atoll(ev);
     // buckets: cooperative worlds (a hash per cell; they also keep a slot
     // snapshot line per bucket) 16 per body; the one-lane and wide forms
     // (linear cell groups, below) 32 per body, so the groups' period spans

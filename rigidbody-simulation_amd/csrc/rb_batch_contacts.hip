@@ -22,29 +22,10 @@
 #include "rb_device.hpp"
 #include "rb_boxes.hpp"
 #include "rb_batch_contacts.hpp"
+#include "rb_contacts.hpp"
 
 namespace rb {
 namespace {
-
-// a real into element o of the caller's array
-template <typename T> __device__ __forceinline__ void put_real(void *a, int64_t o, T v, bool io32) {
-    if (io32) static_cast<float *>(a)[o] = (float)v;
-    else static_cast<double *>(a)[o] = (double)v;
-}
-
-// slot o of the records
-template <typename T>
-__device__ __forceinline__ void put_record(const ContactQuery &q, int64_t o, int32_t partner, int32_t kind, T dist,
-                                           V3<T> pos, V3<T> frame) {
-    q.partner[o] = partner;
-    q.kind[o] = kind;
-    put_real(q.dist, o, dist, q.io32);
-    if (q.pos) { put_real(q.pos, 3 * o, pos.x, q.io32); put_real(q.pos, 3 * o + 1, pos.y, q.io32); put_real(q.pos, 3 * o + 2, pos.z, q.io32); }
-    if (q.frame) {
-        put_real(q.frame, 3 * o, frame.x, q.io32); put_real(q.frame, 3 * o + 1, frame.y, q.io32);
-        put_real(q.frame, 3 * o + 2, frame.z, q.io32);
-    }
-}
 
 // MIXED: the template mixes spheres and boxes (a lane's kind is the
 // template's kind of its body); else spheres only, or (q.box) the one box

@@ -37,6 +37,7 @@
 #include "rb_boxes.hpp"
 #include "rb_batch_frame.hpp"
 #include "rb_batch_contacts.hpp"
+#include "rb_contacts.hpp"
 
 namespace rb {
 namespace {
@@ -249,26 +250,6 @@ void batch_wide_kernel(BatchParams<T> p) {
 // contacts_body of rb_batch_contacts.hip with this file's mapping: a workgroup
 // takes one row of the query, lane = body id.  The list, its order and its
 // layout are that file's.
-
-// a real into element o of the caller's array
-template <typename T> __device__ __forceinline__ void put_real(void *a, int64_t o, T v, bool io32) {
-    if (io32) static_cast<float *>(a)[o] = (float)v;
-    else static_cast<double *>(a)[o] = (double)v;
-}
-
-// slot o of the records
-template <typename T>
-__device__ __forceinline__ void put_record(const ContactQuery &q, int64_t o, int32_t partner, int32_t kind, T dist,
-                                           V3<T> pos, V3<T> frame) {
-    q.partner[o] = partner;
-    q.kind[o] = kind;
-    put_real(q.dist, o, dist, q.io32);
-    if (q.pos) { put_real(q.pos, 3 * o, pos.x, q.io32); put_real(q.pos, 3 * o + 1, pos.y, q.io32); put_real(q.pos, 3 * o + 2, pos.z, q.io32); }
-    if (q.frame) {
-        put_real(q.frame, 3 * o, frame.x, q.io32); put_real(q.frame, 3 * o + 1, frame.y, q.io32);
-        put_real(q.frame, 3 * o + 2, frame.z, q.io32);
-    }
-}
 
 template <typename T, bool BOXES, int BLOCK>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, BOXES ? 1 : 8)))

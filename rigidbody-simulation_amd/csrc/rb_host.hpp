@@ -206,6 +206,19 @@ struct rb_world {
     int32_t tile_backoff = 0, tile_skip = 0;   // eligible runs to step hashed after a roll-back (doubling)
     bool tile_replaying = false;   // tile_finish's replay steps hashed
 
+    // the contact query (rb_api_contacts.hip): a broadphase table of its own
+    // (allocated at the first query; cq_words: its generation and its error
+    // word) for the grid of cq_H buckets and line layout cq_layout, and the
+    // host form's staging (device, pinned twin; at most cq_limit bytes).
+    // Nothing else of the world is written by a query
+    uint32_t *cq_line = nullptr, *cq_spill = nullptr, *cq_words = nullptr;
+    int64_t cq_H = 0;
+    int32_t cq_layout = 0;
+    uint32_t cq_gen = 0;           // the generation of the last query (0: the table holds zeros)
+    char *cq_stage = nullptr, *cq_stage_h = nullptr;
+    size_t cq_stage_bytes = 0;
+    size_t cq_limit = (size_t)256 << 20;   // RBHIP_CONTACT_STAGE_BYTES
+
     int sp() const { return (int)(c % 2); }
 };
 

@@ -1,7 +1,8 @@
 // rb_step.hpp — the hot path on gfx950: the step-kernel body shared by the
 // two step units (rb_step.hip: cooperative, one-lane, box and split forms;
 // rb_step_wide.hip: the wide forms, built with their own scheduling flags).
-// Device code only; included by those two units and nothing else.
+// Device code only; included by those two units and, for candidate_hit, by
+// the contact query (rb_world_contacts.hip), and nothing else.
 //
 // One launch per simulation step (rb::step_kernel), 64-thread workgroups
 // (one wave):

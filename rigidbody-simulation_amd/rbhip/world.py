@@ -8,6 +8,7 @@ boundary in the reference's own layout (qpos stride 7, qvel stride 6).
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import numpy as np
@@ -17,6 +18,51 @@ from ._devarray import _IO_CODES, _device_array, _new_tensor, _pair_typestr
 from .scenes import Scene
 
 COMM_ID_BYTES = 128      # ncclUniqueId (rccl.h NCCL_UNIQUE_ID_BYTES)
+QUERY_PARTNERS = 32      # the partner list of the contact query's search (rb_query_contacts)
+QUERY_NO_LIST = -2       # counts of a body whose list could not be built
+
+
+class WorldContacts:
+    """The contact lists of a world's state (World.query_contacts /
+    query_contacts_device): the fields of BatchContacts for one row, dense
+    arrays with R = max_records slots per body.
+
+    counts (1, count) int32: the true number of contacts of each listed body,
+    also where it exceeds R (then only the first R records are kept); -2 for a
+    body whose list could not be built (more than 32 partners in reach, a
+    non-finite or out-of-range position, or the query's table overflowed).
+    partner, kind (1, count, R) int32 and dist (1, count, R): partner is a
+    global body id or -1 - plane, kind an RB_CK_* code.  pos, frame
+    (1, count, R, 3), or None without geometry: frame is the raw normal from
+    geom1 to geom2 (geom1: the plane; the lower id of two spheres or two
+    boxes; the sphere of a sphere-box pair).  Slots at or past a body's count
+    hold kind -1 and zeros.  truncated: the number of bodies with count > R
+    (None for the device form, which does not wait).  With max_records 0 only
+    counts is set.  first: the id of the first listed body."""
+
+    def __init__(self, max_records, counts, partner, kind, dist, pos, frame, truncated, first=0):
+        self.max_records = max_records
+        self.counts, self.partner, self.kind, self.dist = counts, partner, kind, dist
+        self.pos, self.frame = pos, frame
+        self.truncated = truncated
+        self.first = first
+
+    def to_csr(self):
+        """The lists in the CSR shape of World.contacts(): (counts (count,),
+        partner, kind, dist, pos, frame), the last five flat over the kept
+        records, body by body (pos / frame None without geometry; all five
+        None with max_records 0).  counts stays as returned: past max_records
+        for a truncated body (min(counts, max_records) records are kept), -2
+        for a body without a list (none).  Host arrays only."""
+        cnt = np.asarray(self.counts).reshape(-1)
+        if self.partner is None:
+            return cnt.copy(), None, None, None, None, None
+        R = self.max_records
+        keep = np.arange(R)[None, :] < np.clip(cnt, 0, R)[:, None]
+        out = [cnt.copy()]
+        for a in (self.partner, self.kind, self.dist, self.pos, self.frame):
+            out.append(None if a is None else np.asarray(a).reshape((cnt.size, R) + np.shape(a)[3:])[keep])
+        return tuple(out)
 
 
 class World:
@@ -58,6 +104,13 @@ class World:
         self._n_planes = d.n_planes
         self._any_box = bool(np.any(self._kind != 0))
         self.maxrec = self._maxrec(max_partners)
+        # the bound of rb_query_contacts' staging buffer, read when the world is created
+        try:
+            self._stage_limit = int(os.environ.get("RBHIP_CONTACT_STAGE_BYTES", "0"))
+        except ValueError:
+            self._stage_limit = 0
+        if self._stage_limit <= 0:
+            self._stage_limit = 256 << 20
         n_owned, bpb = C.c_int64(), C.c_int64()
         _lib.check(L.rb_query(h, C.byref(n_owned), C.byref(bpb)), "rb_query")
         self.n_owned = n_owned.value
@@ -275,6 +328,103 @@ class World:
     # ---- parity support -----------------------------------------------------
     def record_contacts(self, enable: bool = True):
         _lib.check(self._L.rb_record_contacts(self._h, int(bool(enable))), "rb_record_contacts")
+
+    # ---- the contact query ---------------------------------------------------
+    def _query_range(self, first, count, max_records, geometry):
+        n = self.scene.n
+        first = int(first)
+        count = n - first if count is None else int(count)
+        if max_records is None:
+            # the scene's bound, as long as one body's slots fit the staging
+            # buffer of the host form (rb_query_contacts)
+            R = 4 * self._n_planes + (4 if self._any_box else 1) * QUERY_PARTNERS
+            per_slot = 8 * (7 if geometry else 1) + 8
+            R = max(0, min(R, (self._stage_limit - 4) // per_slot))
+        else:
+            R = int(max_records)
+        return first, count, R
+
+    def query_contacts(self, first=0, count=None, max_records=None, geometry=True, strict=True) -> WorldContacts:
+        """The contact list of bodies [first, first + count) (count None: up
+        to the last) for the world's current state, as mj_forward generates it
+        (data.contact, collision.py:57, :72-76), in the canonical order of
+        contacts(), with pos and frame.  It steps nothing and changes nothing
+        a step can see; like get_state() it first finishes the world's pending
+        work.  max_records: slots per body (None: the scene's bound, 4 per
+        plane + 32 partners' records; 0: counts only); geometry=False leaves
+        pos and frame out.  A body whose list cannot be built (WorldContacts)
+        raises RbError (EOVERFLOW / EDOM) if strict; with strict=False the
+        arrays are returned with -2 in its counts.  One rank, not under
+        "balls"."""
+        first, count, R = self._query_range(first, count, max_records, geometry)
+        c = max(count, 0)
+        counts = np.zeros((1, c), np.int32)
+        rec = R > 0
+        partner = np.zeros((1, c, R), np.int32) if rec else None
+        kind = np.zeros((1, c, R), np.int32) if rec else None
+        dist = np.zeros((1, c, R)) if rec else None
+        pos = np.zeros((1, c, R, 3)) if rec and geometry else None
+        frame = np.zeros((1, c, R, 3)) if rec and geometry else None
+        nt = C.c_int64()
+        rc = self._L.rb_query_contacts(self._h, first, count, R, _lib.ptr(counts), _lib.ptr(partner), _lib.ptr(kind),
+                                       _lib.ptr(dist), _lib.ptr(pos), _lib.ptr(frame), C.byref(nt))
+        # (EOVERFLOW / EDOM of a query with valid arguments: a body without a list, every array written)
+        if rc != _lib.RB_OK and (strict or rc not in (-75, -33)):
+            _lib.check(rc, "rb_query_contacts")
+        return WorldContacts(R, counts, partner, kind, dist, pos, frame, nt.value, first)
+
+    def query_contacts_device(self, first=0, count=None, max_records=None, geometry=True, dtype=None,
+                              out=None) -> WorldContacts:
+        """query_contacts() into device memory, enqueued on the world's stream
+        without waiting (but a tile-form run's check, as get_state_device): a
+        WorldContacts whose fields are the arrays of `out` (a WorldContacts of
+        an earlier call, or a mapping with the fields' names; its max_records
+        and geometry hold) or new torch tensors: counts, partner and kind
+        int32, dist, pos and frame of `dtype` ("f64" / "f32"; None: the
+        arrays', else the world's).  truncated is None: nothing is read back,
+        and a body without a list shows as -2 in counts alone."""
+        names = ("counts", "partner", "kind", "dist", "pos", "frame")
+        if out is not None:
+            given = {k: (out.get(k) if hasattr(out, "get") else getattr(out, k, None)) for k in names}
+            if given["counts"] is None:
+                raise ValueError("out: counts is required")
+            if given["partner"] is None:
+                R = 0
+            else:
+                try:
+                    R = int(given["partner"].__cuda_array_interface__["shape"][-1])
+                except Exception as exc:
+                    raise TypeError("partner: expected device memory (an object with __cuda_array_interface__), "
+                                    f"got {type(given['partner']).__name__}") from exc
+            if max_records is not None and int(max_records) != R:
+                raise ValueError(f"partner: {R} slots per body, max_records is {int(max_records)}")
+            first, count, _ = self._query_range(first, count, R, geometry)
+        else:
+            given = dict.fromkeys(names)
+            first, count, R = self._query_range(first, count, max_records, geometry)
+        if R < 0:
+            raise ValueError("max_records < 0")
+        ts = _pair_typestr(self.dtype, ("dist", "pos", "frame"), (given["dist"], given["pos"], given["frame"]), dtype)
+        c = max(count, 0)
+        if out is None:
+            given["counts"] = _new_tensor((1, c), "<i4", self.device)
+            if R > 0:
+                given["partner"] = _new_tensor((1, c, R), "<i4", self.device)
+                given["kind"] = _new_tensor((1, c, R), "<i4", self.device)
+                given["dist"] = _new_tensor((1, c, R), ts, self.device)
+                if geometry:
+                    given["pos"] = _new_tensor((1, c, R, 3), ts, self.device)
+                    given["frame"] = _new_tensor((1, c, R, 3), ts, self.device)
+        shapes = {"counts": ((1, c), ("<i4",)), "partner": ((1, c, R), ("<i4",)), "kind": ((1, c, R), ("<i4",)),
+                  "dist": ((1, c, R), (ts,)), "pos": ((1, c, R, 3), (ts,)), "frame": ((1, c, R, 3), (ts,))}
+        ptrs = {k: None if given[k] is None else _device_array(k, given[k], *shapes[k], out=True)[0] for k in names}
+        if R > 0 and c > 0 and None in (ptrs["partner"], ptrs["kind"], ptrs["dist"]):
+            raise ValueError("partner, kind and dist: all three are required with max_records > 0")
+        _lib.check(self._L.rb_query_contacts_dev(self._h, first, count, R, *(ptrs[k] for k in names), _IO_CODES[ts]),
+                   "rb_query_contacts_dev")
+        if R == 0:
+            return WorldContacts(0, given["counts"], None, None, None, None, None, None, first)
+        return WorldContacts(R, *(given[k] for k in names), None, first)
 
     def contacts(self):
         """Contact list of the most recent step, CSR over owned bodies:
