@@ -450,9 +450,10 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * Arrays are environment-major: body k of environment e at row e*M + k.
  * Not covered (use rb_world): contacts recorded inside a step (a batch is
  * asked for the contact list of its current state: rb_batch_contacts), sharding,
- * per-environment kinds or plane counts, more than 256 bodies per
+ * per-environment plane counts, more than 256 bodies per
  * environment; under RB_LAW_BALLS also per-environment planes, applied
- * forces, the contact query and environments of more than 64 bodies.
+ * forces, the contact query, environments of more than 64 bodies and
+ * per-environment body counts and kinds (rb_batch_set_population).
  * A batch handle is not thread-safe; every call that takes host arrays is
  * synchronous (the device-resident boundary below only enqueues).
  *
@@ -477,7 +478,8 @@ int  rb_batch_create(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs)
  * max_partners 32.  Additive to 0.4 (rb_version is unchanged).  A sphere-only
  * or one-box template gives exactly the batch rb_batch_create gives.  Every
  * other rb_batch_* call works on such a batch as on any other (sizes set by
- * rb_batch_set_bodies are per environment, the kinds stay the template's);
+ * rb_batch_set_bodies are per environment, the kinds stay the template's
+ * unless rb_batch_set_population gives every environment its own);
  * rb_batch_set_contact_law(RB_LAW_BALLS) is RB_EUNSUPPORTED: that law takes
  * spheres only. */
 int  rb_batch_create_mixed(rb_batch **out, const rb_scene_desc *scene, int64_t n_envs);
@@ -503,10 +505,49 @@ void rb_batch_destroy(rb_batch *b);
  * src/config/sim_overrides.py:1-28 (one run of the reference per value). */
 int  rb_batch_set_params(rb_batch *b, const double *restitution, const double *friction);
 /* Per-environment body constants: mass [E*M], inertia [E*M*3], size [E*M*3]
- * (as rb_scene_desc; kinds stay the template's); NULL = keep.  Replaces
+ * (as rb_scene_desc; kinds stay the template's, or the population's:
+ * rb_batch_set_population); NULL = keep.  Replaces
  * model.body_mass / body_inertia / geom_size of a per-variant model
  * (collision.py:58-62). */
 int  rb_batch_set_bodies(rb_batch *b, const double *mass, const double *inertia, const double *size);
+/* The population of a batch: per environment a body count and a kind for each
+ * of its M body slots, so that one batch holds scenes of different shapes (an
+ * ensemble of piles of 1 to 8 bodies; single_sphere, single_cube and
+ * multi_sphere4 side by side).  Additive to 0.4 (rb_version is unchanged).
+ * n_bodies [n_envs] (1..M; NULL: every environment holds M bodies);
+ * kind [n_envs*M] RB_BODY_* (NULL: the template's kinds in every environment).
+ * Both NULL: no population; the batch steps with the kernels it stepped with before.
+ *
+ * Bodies 0 .. n_e-1 of environment e are present, slots n_e .. M-1 absent.
+ * Every environment steps bit-identically to an rb_world of its own scene:
+ * the present bodies alone, with their own kinds, under max_partners 32.
+ * Present bodies are a prefix, so body and partner ids are those of the
+ * smaller world.  A uniform population (all counts M, the template's kinds)
+ * gives the same words as no population.
+ *
+ * Absent slots are ordinary storage: the set calls write their rows of state,
+ * constants and forces (validated as ever over all n_envs*M rows) and the get
+ * calls return them bit for bit.  No step reads or writes them: they are
+ * nobody's partner, take no plane contact and cannot fail an environment (a
+ * NaN position there is harmless).  In sampled runs their rows hold zeros in
+ * every sample; in the contact query an absent body has count 0 and unused
+ * slots only (a failed environment still reports -1 for all M bodies).
+ * Bounding radii (here and in rb_batch_set_bodies) follow the population's
+ * kinds; the batch's largest radius skips absent bodies.
+ *
+ * Synchronous: pending work finishes first, under the population it was
+ * enqueued with.  The call touches no state, status or step count and may come
+ * between any two calls; no state is converted.  Any batch accepts it,
+ * whatever its creator and M; a batch of rb_batch_create may receive boxes
+ * this way.  RB_EINVAL for a count outside 1..M or a kind other than
+ * RB_BODY_SPHERE / RB_BODY_BOX in any of the n_envs*M slots (the message names
+ * the environment and the body); RB_EUNSUPPORTED under RB_LAW_BALLS, and
+ * rb_batch_set_contact_law(RB_LAW_BALLS) is RB_EUNSUPPORTED while a
+ * population is set.  A refused call changes nothing.
+ * Not covered: a device-side form of this call (a reset that changes an
+ * environment's body count without the host), the two-ball law,
+ * per-environment plane counts, more than 256 bodies. */
+int  rb_batch_set_population(rb_batch *b, const int32_t *n_bodies, const int32_t *kind);
 /* qpos [n*M*7], qvel [n*M*6] for the environments listed in env_ids[n]
  * (distinct; NULL = all n_envs, in order, n = n_envs).  set clears the listed
  * environments' failed status and step count (a per-environment reset).

@@ -1,6 +1,6 @@
 // rb_api_batch.hip — batched worlds (rb_batch_*; kernels in rb_batch.hip,
 // rb_batch_boxes.hip and, for an environment of more than 64 bodies,
-// rb_batch_wide.hip).
+// rb_batch_wide.hip; with a population set, rb_batch_ragged.hip).
 // E replicas of a template environment of M <= 256 bodies, body b of
 // environment e at slot e * M + b of every device row.  All work is enqueued
 // on the batch's stream (its own, or the caller's: rb_batch_set_stream); the
@@ -11,7 +11,9 @@
 
 #include "rb_batch_contacts.hpp"
 #include "rb_batch_dev.hpp"
+#include "rb_batch_ragged.hpp"
 #include "rb_host.hpp"
+#include "rb_laneplan.hpp"
 #include "rb_sampleplan.hpp"
 
 using namespace rb::host;
@@ -63,6 +65,17 @@ struct rb_batch {
     // environments (allocated on first use, it only grows, at most samp_limit bytes)
     char *con = nullptr;
     size_t con_bytes = 0;
+    // the sizes last given (rb_batch_create, rb_batch_set_bodies): [E * M * 3];
+    // a change of population derives the bounding radii from them again
+    std::vector<double> size;
+    // the population (rb_batch_set_population): while pop_set, the kernels of
+    // rb_batch_ragged.hip step and query the batch
+    bool pop_set = false;
+    bool pop_boxes = false;            // a present body of some environment is a box
+    bool pop_absent = false;           // some environment holds fewer than M bodies
+    std::vector<int32_t> pop_n, pop_kind;       // [E], [E * M]
+    int32_t *d_pop = nullptr;          // one allocation: n_bodies [E], kind [E * M], wave_env0 [waves + 1], lane_row [waves * 64]
+    int32_t pop_waves = 0, pop_epw = 0;
 };
 
 namespace {
@@ -72,7 +85,7 @@ void free_batch(rb_batch *b) {
     (void)hipSetDevice(b->device);
     if (b->own_stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused, b->con};
+                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused, b->con, b->d_pop};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);   // (never the caller's)
@@ -88,6 +101,13 @@ int bput(rb_batch *b, void *dst, const void *src, size_t bytes) {
 double batch_bound_of(int32_t kind, const double *s) {
     return kind == RB_BODY_SPHERE ? s[0] : sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
 }
+
+// the kind of body slot g: the population's, else the template's
+int32_t batch_kind_of(const rb_batch *b, int64_t g) {
+    return b->pop_set ? b->pop_kind[(size_t)g] : b->kind[(size_t)(g % b->M)];
+}
+// is body slot g stepped (a present body)?
+bool batch_present(const rb_batch *b, int64_t g) { return !b->pop_set || g % b->M < b->pop_n[(size_t)(g / b->M)]; }
 
 // the cell size of a world of these bodies (upload_consts; under the two-ball
 // law rb_set_contact_law's, from the reach 2 rmax + tol): the position check
@@ -140,6 +160,28 @@ int batch_put_env(rb_batch *b, void **buf, bool *have, const double *src, int64_
     return RB_OK;
 }
 
+// The bounding radius of every body slot from the sizes last given and the
+// slot's kind, and the batch's largest radius over the bodies that are
+// stepped (an absent slot keeps a radius, which nothing reads).
+int batch_put_bounds(rb_batch *b) {
+    std::vector<double> bound((size_t)b->N);
+    double rmax = 0;
+    for (int64_t g = 0; g < b->N; ++g) {
+        bound[(size_t)g] = batch_bound_of(batch_kind_of(b, g), b->size.data() + 3 * g);
+        if (batch_present(b, g) && bound[(size_t)g] > rmax) rmax = bound[(size_t)g];
+    }
+    WCHK(batch_put_row(b, 7, bound.data(), 1, 0));
+    b->rmax = rmax;
+    batch_set_cell(b);
+    // the snapshots carry the bounding radius
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_batch_bound<T>(dp<Snap<T>>(b->snap, 0), dp<T>(b->consts, 7 * b->N), b->N, b->stream);
+    }));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RB_OK;
+}
+
 template <typename T> StateIO<T> batch_io(rb_batch *b) {
     StateIO<T> p{};
     p.qpos = b->io_q;
@@ -182,8 +224,23 @@ template <typename T> BatchParams<T> batch_params(rb_batch *b, int32_t k, double
     return p;
 }
 
+// the population's device tables (b->d_pop)
+Population batch_population(const rb_batch *b) {
+    Population pop{};
+    pop.n_bodies = b->d_pop;
+    pop.kind = pop.n_bodies + b->E;
+    if (!b->wide) {
+        pop.wave_env0 = pop.kind + b->N;
+        pop.lane_row = pop.wave_env0 + b->pop_waves + 1;
+        pop.waves = b->pop_waves;
+        pop.epw_max = b->pop_epw;
+    }
+    return pop;
+}
+
 // one launch of the batch's step kernel (rec: the recording instance)
 template <typename T> hipError_t batch_launch(rb_batch *b, const BatchParams<T> &p, bool rec) {
+    if (b->pop_set) return launch_ragged_step<T>(p, batch_population(b), b->pop_boxes, rec, b->stream);
     if (b->wide) return launch_batch_wide<T>(p, b->mixed, rec, b->stream);
     if (b->mixed) return launch_batch_mixed<T>(p, rec, b->stream);
     return launch_batch_step<T>(p, b->box, b->law == RB_LAW_BALLS, rec, b->stream);
@@ -288,6 +345,13 @@ int batch_enqueue_sampled(rb_batch *b, const SampleLaunch &l, char *slots, int64
         p.samp_first = (int32_t)l.first;
         p.samp_slots = (int32_t)fit;
         p.samp_rows = rows;
+        // absent bodies have no lane (or an idle one): their rows of the slots
+        // this launch fills hold zeros
+        if (b->pop_set && b->pop_absent) {
+            const size_t slot = (size_t)b->N * (size_t)rows * sizeof(T);
+            const hipError_t rc = hipMemsetAsync(slots + (size_t)l.first * slot, 0, (size_t)l.samples * slot, b->stream);
+            if (rc != hipSuccess) return rc;
+        }
         return batch_launch<T>(b, p, true);
     }));
     return RB_OK;
@@ -431,6 +495,7 @@ int batch_launch_contacts(rb_batch *b, const ContactQuery &q) {
     HIPCHK(by_real(b->dtype, [&](auto t) {
         using T = decltype(t);
         const BatchParams<T> p = batch_params<T>(b, 0, 1.0, 0.0, 0.0, 0.0);
+        if (b->pop_set) return launch_ragged_contacts<T>(p, batch_population(b), q, b->pop_boxes, b->stream);
         return b->wide ? launch_batch_wide_contacts<T>(p, q, b->mixed, b->stream)
                        : launch_batch_contacts<T>(p, q, b->mixed, b->stream);
     }));
@@ -494,22 +559,79 @@ int rb_batch_set_bodies(rb_batch *b, const double *mass, const double *inertia, 
         for (int j = 0; j < 3; ++j) WCHK(batch_put_row(b, 1 + j, inertia, 3, j));
     if (size) {
         for (int j = 0; j < 3; ++j) WCHK(batch_put_row(b, 4 + j, size, 3, j));
-        std::vector<double> bound((size_t)b->N);
-        double rmax = 0;
-        for (int64_t g = 0; g < b->N; ++g) {
-            bound[(size_t)g] = batch_bound_of(b->kind[(size_t)(g % b->M)], size + 3 * g);
-            if (bound[(size_t)g] > rmax) rmax = bound[(size_t)g];
-        }
-        WCHK(batch_put_row(b, 7, bound.data(), 1, 0));
-        b->rmax = rmax;
-        batch_set_cell(b);
-        // the snapshots carry the bounding radius
-        HIPCHK(by_real(b->dtype, [&](auto t) {
-            using T = decltype(t);
-            return launch_batch_bound<T>(dp<Snap<T>>(b->snap, 0), dp<T>(b->consts, 7 * b->N), b->N, b->stream);
-        }));
-        HIPCHK(hipStreamSynchronize(b->stream));
+        b->size.assign(size, size + 3 * (size_t)b->N);
+        WCHK(batch_put_bounds(b));
     }
+    return RB_OK;
+}
+
+int rb_batch_set_population(rb_batch *b, const int32_t *n_bodies, const int32_t *kind) {
+    ApiScope api_scope_(b ? b->device : -1);
+    if (!b) return fail(RB_EINVAL, "null batch");
+    const bool set = n_bodies || kind;
+    if (n_bodies)
+        for (int64_t e = 0; e < b->E; ++e)
+            if (n_bodies[e] < 1 || n_bodies[e] > b->M)
+                return fail(RB_EINVAL, "environment %lld: a body count of %d is outside [1, %d]", (long long)e, n_bodies[e], b->M);
+    if (kind)
+        for (int64_t g = 0; g < b->N; ++g)
+            if (kind[g] != RB_BODY_SPHERE && kind[g] != RB_BODY_BOX)
+                return fail(RB_EINVAL, "environment %lld, body %lld: bad kind %d", (long long)(g / b->M),
+                            (long long)(g % b->M), kind[g]);
+    if (set && b->law == RB_LAW_BALLS)
+        return fail(RB_EUNSUPPORTED, "the two-ball law takes no population: its batches are uniform");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));         // pending work finishes under the population it was enqueued with
+    // the new population, complete before the batch changes
+    std::vector<int32_t> pn, pk;
+    LanePlan plan;
+    int32_t *tables = nullptr;
+    bool boxes = false, absent = false;
+    if (set) {
+        if (n_bodies) pn.assign(n_bodies, n_bodies + b->E);
+        else pn.assign((size_t)b->E, b->M);
+        if (kind) pk.assign(kind, kind + b->N);
+        else
+            for (int64_t g = 0; g < b->N; ++g) pk.push_back(b->kind[(size_t)(g % b->M)]);
+        for (int64_t g = 0; g < b->N; ++g) {
+            const bool present = g % b->M < pn[(size_t)(g / b->M)];
+            boxes = boxes || (present && pk[(size_t)g] == RB_BODY_BOX);
+            absent = absent || !present;
+        }
+        std::vector<int32_t> h(pn);
+        h.insert(h.end(), pk.begin(), pk.end());
+        if (!b->wide) {
+            if (!lane_plan(pn.data(), b->E, b->M, plan)) return fail(RB_EINVAL, "no lane plan for this population");
+            h.insert(h.end(), plan.wave_env0.begin(), plan.wave_env0.end());
+            h.insert(h.end(), plan.lane_row.begin(), plan.lane_row.end());
+        }
+        HIPCHK(hipMalloc((void **)&tables, sizeof(int32_t) * h.size()));
+        if (int rc = bput(b, tables, h.data(), sizeof(int32_t) * h.size())) {
+            (void)hipFree(tables);
+            return rc;
+        }
+    }
+    // commit; the bounding radii follow the kinds
+    const bool was_set = b->pop_set, was_boxes = b->pop_boxes, was_absent = b->pop_absent;
+    const int32_t was_waves = b->pop_waves, was_epw = b->pop_epw;
+    const double was_rmax = b->rmax;
+    b->pop_n.swap(pn);
+    b->pop_kind.swap(pk);
+    b->pop_set = set; b->pop_boxes = boxes; b->pop_absent = absent;
+    b->pop_waves = plan.waves; b->pop_epw = plan.epw_max;
+    if (int rc = batch_put_bounds(b)) {
+        // (a device error; the host side is put back, and so are the radii, where the device still answers)
+        b->pop_n.swap(pn);
+        b->pop_kind.swap(pk);
+        b->pop_set = was_set; b->pop_boxes = was_boxes; b->pop_absent = was_absent;
+        b->pop_waves = was_waves; b->pop_epw = was_epw;
+        b->rmax = was_rmax;
+        (void)batch_put_bounds(b);
+        if (tables) (void)hipFree(tables);
+        return rc;
+    }
+    if (b->d_pop) (void)hipFree(b->d_pop);
+    b->d_pop = tables;
     return RB_OK;
 }
 
@@ -558,6 +680,9 @@ int rb_batch_set_contact_law(rb_batch *b, int32_t law, double tol) {
     if (law != RB_LAW_MUJOCO && law != RB_LAW_BALLS) return fail(RB_EINVAL, "unknown contact law %d", law);
     if (!(tol >= 0) || !(tol < 1e6)) return fail(RB_EINVAL, "tol must be finite and >= 0");
     if (law == RB_LAW_BALLS) {
+        if (b->pop_set)
+            return fail(RB_EUNSUPPORTED, "the two-ball law takes no population (clear it first: rb_batch_set_population "
+                                         "with NULL, NULL)");
         if (b->box || b->mixed) return fail(RB_EUNSUPPORTED, "the two-ball law takes spheres only");
         if (b->wide)
             return fail(RB_EUNSUPPORTED, "the two-ball law takes environments of at most %d bodies (this one has %d)",

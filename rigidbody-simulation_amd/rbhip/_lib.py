@@ -87,6 +87,7 @@ SIGNATURES = {
     "rb_batch_destroy": (None, [_P]),
     "rb_batch_set_params": (C.c_int, [_P, _P, _P]),
     "rb_batch_set_bodies": (C.c_int, [_P, _P, _P, _P]),
+    "rb_batch_set_population": (C.c_int, [_P, _P, _P]),
     "rb_batch_set_state": (C.c_int, [_P, _P, _I64, _P, _P]),
     "rb_batch_get_state": (C.c_int, [_P, _P, _I64, _P, _P]),
     "rb_batch_step": (C.c_int, [_P, _I64, _D, _D, _D, _D, C.POINTER(_I64)]),

@@ -15,6 +15,11 @@ included; from_scenes over a list of seeds is an ensemble of piles.  A
 scene holds up to 256 bodies: up to 64 an environment is (a part of) one
 wave, from 65 on one workgroup of 2 to 4 waves (a wide batch), with the same
 interface and the same bits; only the two-ball law stops at 64.
+The environments need not hold the same scene shape: a population
+(set_population, from_ragged_scenes) gives every environment its own body
+count (1..M) and its own kinds.  Bodies past an environment's count are
+absent: their rows are storage that no step reads or writes, sampled runs
+hold zeros there and the contact query gives them count 0.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
 multi_sphere_logger.py), one per environment, sampled on the device.
@@ -48,7 +53,9 @@ class BatchContacts:
     two spheres or two boxes; the sphere of a sphere-box pair).  Slots at or
     past a body's count hold kind -1 and zeros.  truncated: the number of
     bodies with count > R (None for the device form, which does not wait).
-    With max_records 0 only counts is set."""
+    With max_records 0 only counts is set.  An absent body (a slot past its
+    environment's body count: BatchWorld.set_population) has count 0 and
+    unused slots only, and is nobody's partner."""
 
     def __init__(self, max_records, counts, partner, kind, dist, pos, frame, truncated):
         self.max_records = max_records
@@ -116,6 +123,7 @@ class BatchWorld:
         _lib.check(getattr(L, create)(C.byref(h), C.byref(d), self.n_envs), create)
         self._h = h
         self._L = L
+        self._population = None
         E, M = self.n_envs, self.n_bodies
         if law != "mujoco":
             try:
@@ -155,6 +163,55 @@ class BatchWorld:
             b.set_bodies(mass=np.stack([sc.mass for sc in scenes]), inertia=np.stack([sc.inertia for sc in scenes]),
                          size=np.stack([sc.size for sc in scenes]))
             b.set_state(np.stack([sc.qpos0 for sc in scenes]), np.stack([sc.qvel0 for sc in scenes]))
+        except Exception:
+            b.close()
+            raise
+        return b
+
+    @classmethod
+    def from_ragged_scenes(cls, scenes, **kw):
+        """A batch with one environment per Scene of `scenes`, which may
+        differ in body count and kinds (an ensemble of piles of 1 to 8
+        bodies; single_sphere, single_cube and multi_sphere4 side by side).
+        M is the largest body count and the template the first scene of that
+        size; every environment's population is its scene's count and kinds
+        (set_population).  Shorter scenes are padded with absent bodies: mass
+        and inertia 1, the template's size row, pose (0, 0, 0, 1, 0, 0, 0),
+        zero velocity, the template's kind.  Everything from_scenes takes per
+        scene is taken here too.  The scenes must agree in plane count, dt,
+        threshold and normal convention (ValueError naming the first scene
+        that does not, before any batch is created).  kw: the constructor's."""
+        scenes = list(scenes)
+        if not scenes:
+            raise ValueError("from_ragged_scenes: no scene given")
+        M = max(sc.n for sc in scenes)
+        t = next(sc for sc in scenes if sc.n == M)
+        for k, sc in enumerate(scenes):
+            for what, same in (("plane count", np.shape(sc.planes)[0] == np.shape(t.planes)[0]),
+                               ("dt", sc.dt == t.dt), ("threshold", sc.threshold == t.threshold),
+                               ("normal convention", sc.normal_convention == t.normal_convention)):
+                if not same:
+                    raise ValueError(f"from_ragged_scenes: scene {k} ({sc.name!r}) differs from the template "
+                                     f"({t.name!r}) in its {what}")
+        E = len(scenes)
+        n = np.array([sc.n for sc in scenes], np.int32)
+        kinds = np.tile(np.asarray(t.kind, np.int32), (E, 1))
+        mass, inertia = np.ones((E, M)), np.ones((E, M, 3))
+        size = np.tile(np.asarray(t.size, np.float64), (E, 1, 1))
+        qpos, qvel = np.zeros((E, M, 7)), np.zeros((E, M, 6))
+        qpos[:, :, 3] = 1.0
+        for e, sc in enumerate(scenes):
+            kinds[e, :sc.n], mass[e, :sc.n], inertia[e, :sc.n], size[e, :sc.n] = sc.kind, sc.mass, sc.inertia, sc.size
+            qpos[e, :sc.n], qvel[e, :sc.n] = sc.qpos0, sc.qvel0
+        b = cls(t, E, **kw)
+        try:
+            b.set_population(n, kinds)
+            if np.shape(t.planes)[0]:
+                b.set_planes(np.stack([np.asarray(sc.planes, np.float64) for sc in scenes]))
+            b.set_gravity(np.stack([np.asarray(sc.gravity, np.float64) for sc in scenes]))
+            b.set_params(restitution=[sc.restitution for sc in scenes], friction=[sc.friction for sc in scenes])
+            b.set_bodies(mass=mass, inertia=inertia, size=size)
+            b.set_state(qpos, qvel)
         except Exception:
             b.close()
             raise
@@ -208,6 +265,32 @@ class BatchWorld:
         E, M = self.n_envs, self.n_bodies
         m, i, s = self._arr(mass, (E, M)), self._arr(inertia, (E, M, 3)), self._arr(size, (E, M, 3))
         _lib.check(self._L.rb_batch_set_bodies(self._h, _lib.ptr(m), _lib.ptr(i), _lib.ptr(s)), "rb_batch_set_bodies")
+
+    def set_population(self, n_bodies=None, kinds=None):
+        """Per-environment body counts n_bodies (E,) in 1..M (None: M
+        everywhere) and kinds (E, M), 0 sphere / 1 box (None: the template's
+        in every environment).  Bodies 0..n_e-1 of environment e are present
+        and step bit-identically to a World of those bodies alone; the rest
+        are absent: storage that set_* / get_* write and return as ever and
+        that no step reads or writes.  Both None: no population again.  May
+        be called between any two calls; it changes no state.  Not under
+        "balls" (RbError, RB_EUNSUPPORTED)."""
+        E, M = self.n_envs, self.n_bodies
+        n = None if n_bodies is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_bodies, np.int32), (E,)))
+        k = None if kinds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(kinds, np.int32), (E, M)))
+        _lib.check(self._L.rb_batch_set_population(self._h, _lib.ptr(n), _lib.ptr(k)), "rb_batch_set_population")
+        if n is None and k is None:
+            self._population = None
+        else:
+            self._population = (np.full(E, M, np.int32) if n is None else n.copy(),
+                                np.tile(np.asarray(self.scene.kind, np.int32), (E, 1)) if k is None else k.copy())
+
+    @property
+    def population(self):
+        """(n_bodies (E,) int32, kinds (E, M) int32) as last set, or None
+        without a population."""
+        pop = getattr(self, "_population", None)
+        return None if pop is None else (pop[0].copy(), pop[1].copy())
 
     def set_planes(self, planes):
         """Per-environment planes (E, P, 6): normal xyz, point xyz; P is the
@@ -305,6 +388,8 @@ class BatchWorld:
             return int(max_records)
         M, P = self.n_bodies, int(np.shape(self.scene.planes)[0])
         mixed = M > 1 and bool(np.any(np.asarray(self.scene.kind) != 0))
+        if self.population is not None:
+            mixed = M > 1 and bool(np.any(self.population[1] != 0))
         return min(16, 4 * P + (4 if mixed else 1) * (M - 1))
 
     def contacts(self, envs=None, max_records=None, geometry=True) -> BatchContacts:

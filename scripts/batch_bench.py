@@ -63,6 +63,20 @@ of the same batch, and the host form contacts(R) against get_state(),
 alternating; seconds per call.  With --box-pile NX,NY,LAYERS the scene is that
 pile (the mixed-template instance of the query's kernel).
 
+--ragged LO,HI: instead, an ensemble of E scenes whose body counts are spread
+evenly over LO..HI (--ragged-scene flat_spheres: rows of spheres; box_pile:
+columns of two cubes, the first n bodies), f64.  Three measurements in one
+process, alternating rep by rep: (1) the ensemble as one batch with a
+population (BatchWorld.from_ragged_scenes: the lanes packed by body count);
+(2) what had to be done without populations: one uniform batch per distinct
+body count, stepped one after another, times summed; (3) for a uniform
+ensemble (all counts HI), a batch with the uniform population set (the ragged
+kernels) against the same batch with none (the kernels of a batch without
+population): the price of the tables and the per-environment kinds.
+"packed_over_unpacked" is (1) over the ragged rate of (3): the ragged kernels
+on E x HI lanes' worth of work, what the ensemble would cost with the fixed
+mapping.  Writes to profiles/batch_ragged/ unless --out is given.
+
 Prints one JSON line and writes it to --out (default
 profiles/batch/batch_bench.json).  Needs the GPU: there is no fallback.
 """
@@ -377,6 +391,74 @@ def bench_contacts(rb, sc, E, R, settle, reps, dtype, calls=20):
     return res
 
 
+def ragged_scene(variant, n, seed):
+    """A scene of n bodies: a row of spheres, or the first n bodies of columns of two cubes."""
+    from rbhip import scenes
+    if variant == "flat_spheres":
+        return scenes.flat_spheres(n, 1, seed=seed, spacing=0.19)
+    sc = scenes.box_pile((n + 1) // 2, 1, 2, seed=seed, sphere_every=0)
+    return sc.with_(kind=sc.kind[:n], mass=sc.mass[:n], inertia=sc.inertia[:n], size=sc.size[:n], qpos0=sc.qpos0[:n],
+                    qvel0=sc.qvel0[:n])
+
+
+def bench_ragged(rb, variant, lo, hi, E, steps, reps, seeds=16):
+    """Environment-steps per second of (1) the ragged ensemble as one batch,
+    (2) one uniform batch per distinct body count, stepped one after another,
+    (3) a uniform ensemble of hi bodies with and without a population;
+    alternating rep by rep in one process."""
+    counts = [lo + k % (hi - lo + 1) for k in range(E)]
+    cache = {}
+
+    def scene(n, k):
+        key = (n, k % seeds)
+        if key not in cache:
+            cache[key] = ragged_scene(variant, n, k % seeds)
+        return cache[key]
+
+    scs = [scene(n, k) for k, n in enumerate(counts)]
+    groups = {n: [sc for sc in scs if sc.n == n] for n in sorted(set(counts))}
+    full = [scene(hi, k) for k in range(E)]
+    rates = {"ragged": [], "per_shape": [], "uniform_plain": [], "uniform_ragged": []}
+
+    def timed(b, q, v):
+        b.set_state(q, v)
+        t0 = time.perf_counter()
+        failed = b.step(steps)                          # synchronous
+        dt = time.perf_counter() - t0
+        if failed:
+            raise RuntimeError(f"{failed} environments failed")
+        return dt
+
+    def state(b):
+        return b.get_state()
+
+    shapes = [rb.BatchWorld.from_scenes(g) for g in groups.values()]
+    try:
+        with rb.BatchWorld.from_ragged_scenes(scs) as ragged, rb.BatchWorld.from_scenes(full) as plain, \
+                rb.BatchWorld.from_scenes(full) as uni:
+            uni.set_population(np.full(E, hi), np.tile(full[0].kind, (E, 1)))
+            every = [ragged, plain, uni] + shapes
+            start = [state(b) for b in every]           # the initial states, before the warm-up
+            for b in every:
+                b.step(steps)                           # warm-up
+            for _ in range(reps):
+                rates["ragged"].append(E * steps / timed(ragged, *start[0]))
+                rates["per_shape"].append(E * steps / sum(timed(b, *st) for b, st in zip(shapes, start[3:])))
+                rates["uniform_plain"].append(E * steps / timed(plain, *start[1]))
+                rates["uniform_ragged"].append(E * steps / timed(uni, *start[2]))
+            same = bool(np.array_equal(_words(plain.get_state()[0]), _words(uni.get_state()[0])))
+    finally:
+        for b in shapes:
+            b.close()
+    out = {k: _summary(v) for k, v in rates.items()}
+    out.update(present_bodies=int(sum(counts)), lanes_fixed_mapping=E * hi, distinct_shapes=len(groups),
+               uniform_identical=same)
+    out["ragged_over_per_shape"] = out["ragged"]["median"] / out["per_shape"]["median"]
+    out["uniform_ragged_over_plain"] = out["uniform_ragged"]["median"] / out["uniform_plain"]["median"]
+    out["packed_over_unpacked"] = out["ragged"]["median"] / out["uniform_ragged"]["median"]
+    return out
+
+
 def bench_world(rb, sc, steps, reps, dtype, law="mujoco", **kw):
     with (rb.World(sc, dtype=dtype, **kw) if law == "mujoco" else rb.World(sc, dtype=dtype, law=law)) as w:
         w.step(steps)                                   # warm-up (captures the step graph)
@@ -413,8 +495,14 @@ def main():
                     help="time run_sampled_device(steps, EVERY) against run_sampled(steps, EVERY)")
     ap.add_argument("--contacts", type=int, default=-1, metavar="R",
                     help="time the contact query with R records per body, after --steps settling steps")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "batch_bench.json"))
+    ap.add_argument("--ragged", default="", metavar="LO,HI",
+                    help="an ensemble with body counts spread over LO..HI: one ragged batch against one batch per shape")
+    ap.add_argument("--ragged-scene", default="flat_spheres", choices=["flat_spheres", "box_pile"])
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if not a.out:
+        a.out = os.path.join(ROOT, "profiles", "batch_ragged", f"ragged_{a.ragged_scene}_{a.ragged.replace(',', '_')}.json") \
+            if a.ragged else os.path.join(ROOT, "profiles", "batch", "batch_bench.json")
 
     import rbhip
     from rbhip import scenes
@@ -425,7 +513,16 @@ def main():
                version=rbhip.load().rb_version().decode())
     if a.law != "mujoco":
         res["law"] = a.law
-    if a.contacts >= 0:
+    if a.ragged:
+        if a.law != "mujoco" or a.dtype != "f64" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or \
+                a.sampled_device or a.contacts >= 0 or a.box_pile or a.wide_pile:
+            raise SystemExit("--ragged: on its own, f64, under the default law")
+        lo, hi = (int(t) for t in a.ragged.split(","))
+        if not 1 <= lo <= hi <= 256:
+            raise SystemExit("--ragged LO,HI: 1 <= LO <= HI <= 256")
+        res.update(scene=f"ragged {a.ragged_scene}", bodies_per_env=hi, counts=f"{lo}..{hi}")
+        res["ragged"] = {str(E): bench_ragged(rbhip, a.ragged_scene, lo, hi, E, a.steps, a.reps) for E in a.envs}
+    elif a.contacts >= 0:
         if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or a.sampled_device:
             raise SystemExit("--contacts: on its own (with --box-pile for a mixed template), under the default law")
         if a.box_pile:
