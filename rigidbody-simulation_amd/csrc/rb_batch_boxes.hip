@@ -11,8 +11,8 @@
 // touch in the same step: DESIGN 2.5); the partners' kinds and half extents
 // are put into LDS once per launch; a box-involved pair is a partner when the
 // bounding spheres overlap (candidate_hit, rb_step.hpp) and is evaluated by
-// solve_box_pair below, body_update's pair block, from step-start data of
-// both bodies.  Every other body of the environment is
+// solve_box_pair (rb_batch_body.hpp), body_update's pair block, from
+// step-start data of both bodies.  Every other body of the environment is
 // visited in ascending id, which is the order of a world's sorted partner
 // list, so an environment steps bit-identically to a world of its scene.
 //
@@ -20,50 +20,15 @@
 // SIMD, so the kernel is built as box_kernel is (rb_step.hip): one wave per
 // SIMD, register arrays indexed by compile-time constants only, the clipping
 // polygon of box_box a column of 48 reals per lane in LDS.
-#include "rb_device.hpp"
-#include "rb_grid.hpp"
-#include "rb_internal.hpp"
-#include "rb_body.hpp"
-#include "rb_boxes.hpp"
-#include "rb_batch_frame.hpp"
+//
+// The step below is the text batch_step_body (rb_batch_body.hpp) was made
+// from.  This kernel alone stays off it: on the body its instances kept
+// registers and LDS, and a pile of 4 bodies ran 0.5 % slower in all three
+// processes of the A/B (cause not found; DESIGN 4.3, profiles/batch_unify).
+// A change to the step sequence is made there and here.
+#include "rb_batch_body.hpp"
 
 namespace rb {
-
-// K2, the box-involved pair of body i (kind, centre x, orientation M, size
-// sz) with partner j (kind kj, step-start centre cj, orientation Mj — read
-// for a box only —, half extents hj, radius rj where it is a sphere), from
-// step-start data of both bodies (rb_boxes.hpp), in MuJoCo's geom order:
-// sphere before box, boxes by id.  One contact per emitted point, in
-// generation order.  poly, ps: the lane's clipping polygon column in LDS.
-// This is the pair block of body_update (rb_step.hpp), a second copy of its
-// text: moved into a function that both call, box_kernel's f32 instances
-// allocated 247 registers instead of 249, and body_update's
-// code is pinned.
-template <typename T>
-__device__ __forceinline__ void solve_box_pair(const StepParams<T> &p, int32_t l, int32_t i, int32_t j, int32_t kind,
-                                               int32_t kj, V3<T> x, const M3<T> &M, V3<T> sz, V3<T> cj, T rj,
-                                               const M3<T> &Mj, V3<T> hj, T m, T k, LazyInvI<T> &invI, V3<T> &v,
-                                               V3<T> &w, int32_t &nrec, T *poly, int ps) {
-    auto emit = [&](const Contact<T> &con, int ck, bool self_g1) {
-        record(p, l, nrec, j, ck, con.dist);
-        const V3<T> n = (p.oriented && self_g1) ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
-        solve_contact(p, con, x, n, m, k, invI, v, w);
-    };
-    // geom1: the sphere of a sphere-box pair, else the lower id
-    // (one call of each primitive, operands selected)
-    const bool g1 = (kind == 0 && kj != 0) || (kind != 0 && kj != 0 && i < j);
-    const V3<T> p1 = g1 ? x : cj, p2 = g1 ? cj : x;
-    const V3<T> h1 = g1 ? sz : hj, h2 = g1 ? hj : sz;
-    M3<T> M1, M2;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) { M1.a[c] = g1 ? M.a[c] : Mj.a[c]; M2.a[c] = g1 ? Mj.a[c] : M.a[c]; }
-    if (kind == 0 || kj == 0) {
-        Contact<T> con;
-        if (sphere_box(p1, g1 ? sz.x : rj, p2, M2, h2, con)) emit(con, CK_SPHERE_BOX, g1);
-    } else {
-        box_box(p1, M1, h1, p2, M2, h2, poly, ps, [&](const Contact<T> &c, int ck) { emit(c, ck, g1); });
-    }
-}
 
 // REC: the recording instance of a sampled run
 // ENVS: per-environment planes, gravity or applied forces are set
@@ -226,8 +191,7 @@ void batch_mixed_kernel(BatchParams<T> p) {
 template <typename T> hipError_t launch_batch_mixed(const BatchParams<T> &p, bool rec, hipStream_t s) {
     if (p.E <= 0 || p.k <= 0) return hipSuccess;
     if (!p.cs.kind || p.M < 2 || p.M > BATCH_BLOCK || p.n_planes < 0 || p.n_planes > MAX_PLANES) return hipErrorInvalidValue;
-    if (rec && (!p.samp || p.every < 1 || p.phase < 1 || p.phase > p.every || (p.samp_rows != 7 && p.samp_rows != 13)))
-        return hipErrorInvalidValue;
+    if (rec && !rec_ok(p)) return hipErrorInvalidValue;
     const int64_t epw = BATCH_BLOCK / p.M;
     const unsigned blocks = (unsigned)((p.E + epw - 1) / epw);
     as_constant(rec, [&](auto REC) {

@@ -23,6 +23,7 @@
 #include "rb_boxes.hpp"
 #include "rb_batch_contacts.hpp"
 #include "rb_contacts.hpp"
+#include "rb_batch_checks.hpp"
 
 namespace rb {
 namespace {
@@ -176,11 +177,8 @@ void batch_contacts_boxes_kernel(BatchParams<T> p, ContactQuery q) {
 template <typename T>
 hipError_t launch_batch_contacts(const BatchParams<T> &p, const ContactQuery &q, bool mixed, hipStream_t s) {
     if (q.n <= 0) return hipSuccess;
-    if (p.M < 1 || p.M > BATCH_BLOCK || p.n_planes < 0 || p.n_planes > MAX_PLANES || q.R < 0 || !q.counts)
-        return hipErrorInvalidValue;
-    if (q.R > 0 && (!q.partner || !q.kind || !q.dist)) return hipErrorInvalidValue;
+    if (!query_ok(p, q, 1, BATCH_BLOCK)) return hipErrorInvalidValue;
     if (mixed ? !p.cs.kind || p.M < 2 : q.box && p.M != 1) return hipErrorInvalidValue;
-    if (!q.ids && (q.env0 < 0 || q.env0 + q.n > p.E)) return hipErrorInvalidValue;
     const int64_t epw = BATCH_BLOCK / p.M;
     const unsigned blocks = (unsigned)((q.n + epw - 1) / epw);
     if (mixed) hipLaunchKernelGGL((batch_contacts_boxes_kernel<T>), dim3(blocks), dim3(BATCH_BLOCK), 0, s, p, q);

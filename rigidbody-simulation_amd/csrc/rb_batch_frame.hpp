@@ -1,10 +1,14 @@
 // rb_batch_frame.hpp — the frame the batch step kernels share (rb_batch.hip:
 // batch_step_kernel, batch_balls_kernel; rb_batch_boxes.hip:
-// batch_mixed_kernel): the sample store of a recording instance, the wave's
-// per-environment planes in dynamic LDS, the step constants, the sampling
-// tick and the epilogue.
-// (The lane mapping is not part of it: as a function it compiled the plain
-// batch_step_kernel instances to different code, measured 2 % slower: DESIGN 4.3.)
+// batch_mixed_kernel; rb_batch_body.hpp: batch_step_body): the sample store of
+// a recording instance, the wave's per-environment planes in dynamic LDS, the
+// step constants, the sampling tick and the epilogue.
+// (The lane mapping is not part of it.  For the plain batch_step_kernel a
+// mapping function compiled the instances to different code, measured 2 %
+// slower: DESIGN 4.3, and that kernel computes it inline.  The kernels on
+// batch_step_body compute theirs inline too and pass the values: there the
+// shared body kept registers, LDS and occupancy and measured no slower,
+// profiles/batch_unify.)
 #pragma once
 
 #include <type_traits>

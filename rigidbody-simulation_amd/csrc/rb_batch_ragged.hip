@@ -5,12 +5,12 @@
 // batches and the queries), are nobody's partner, take no plane contact,
 // cannot fail their environment and are never stored.
 //
-// A step is batch_mixed_kernel's (BOXES; rb_batch_boxes.hip) or
-// batch_step_kernel's sphere path (!BOXES; rb_batch.hip), from the same
-// functions (rb_body.hpp, rb_device.hpp, rb_boxes.hpp) in the same frame
-// (rb_batch_frame.hpp): partners in ascending id over the present bodies of
-// the environment, which are a prefix, so the ids are those of a world of the
-// present bodies alone and an environment steps bit-identically to it.
+// A step is batch_step_body (rb_batch_body.hpp), one text for this unit's and
+// rb_batch_wide.hip's step kernels, with the population's kind and count handed in:
+// partners in ascending id over the present bodies of the environment, which
+// are a prefix, so the ids are those of a world of the present bodies alone
+// and an environment steps bit-identically to it.  The two step kernels below
+// are their mappings alone.
 //
 // One-wave batches (M <= 64), ragged_step_kernel: the lanes are packed by the
 // host's plan (rb_laneplan.hpp).  A lane reads its row e * M + b from the
@@ -27,52 +27,19 @@
 // Per-environment planes, gravity and forces are not a template parameter
 // here: the planes are always read from the wave's block in dynamic LDS
 // (filled from the batch's rows, or with the template's planes), gravity and
-// forces are tested at run time as the ENVS instances test them.
+// forces are tested at run time: the body's ENVS instances.
 //
 // The queries (ragged_contacts_kernel, ragged_wide_contacts_kernel) keep the
 // fixed E x M mapping of rb_batch_contacts.hip / rb_batch_wide.hip: a query is
 // one pass into a dense (n, M, R) layout; an absent body writes count 0 (-1 in
 // a failed environment) and unused slots.
 // Built once per real type: RB_INST = 1 fp64, 2 fp32.
-#include "rb_device.hpp"
-#include "rb_grid.hpp"
-#include "rb_internal.hpp"
-#include "rb_body.hpp"
-#include "rb_boxes.hpp"
-#include "rb_batch_frame.hpp"
-#include "rb_batch_ragged.hpp"
+#include "rb_batch_body.hpp"
 #include "rb_contacts.hpp"
+#include "rb_batch_ragged.hpp"
 
 namespace rb {
 namespace {
-
-// solve_box_pair of rb_batch_boxes.hip, a further copy of its text (as in
-// rb_batch_wide.hip: that unit's kernels are pinned to the code they compile to).
-template <typename T>
-__device__ __forceinline__ void solve_box_pair(const StepParams<T> &p, int32_t l, int32_t i, int32_t j, int32_t kind,
-                                               int32_t kj, V3<T> x, const M3<T> &M, V3<T> sz, V3<T> cj, T rj,
-                                               const M3<T> &Mj, V3<T> hj, T m, T k, LazyInvI<T> &invI, V3<T> &v,
-                                               V3<T> &w, int32_t &nrec, T *poly, int ps) {
-    auto emit = [&](const Contact<T> &con, int ck, bool self_g1) {
-        record(p, l, nrec, j, ck, con.dist);
-        const V3<T> n = (p.oriented && self_g1) ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
-        solve_contact(p, con, x, n, m, k, invI, v, w);
-    };
-    // geom1: the sphere of a sphere-box pair, else the lower id
-    // (one call of each primitive, operands selected)
-    const bool g1 = (kind == 0 && kj != 0) || (kind != 0 && kj != 0 && i < j);
-    const V3<T> p1 = g1 ? x : cj, p2 = g1 ? cj : x;
-    const V3<T> h1 = g1 ? sz : hj, h2 = g1 ? hj : sz;
-    M3<T> M1, M2;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) { M1.a[c] = g1 ? M.a[c] : Mj.a[c]; M2.a[c] = g1 ? Mj.a[c] : M.a[c]; }
-    if (kind == 0 || kj == 0) {
-        Contact<T> con;
-        if (sphere_box(p1, g1 ? sz.x : rj, p2, M2, h2, con)) emit(con, CK_SPHERE_BOX, g1);
-    } else {
-        box_box(p1, M1, h1, p2, M2, h2, poly, ps, [&](const Contact<T> &c, int ck) { emit(c, ck, g1); });
-    }
-}
 
 // The planes of `count` environments from `env0` on into the block
 // [plane][component][stride] (EnvPlanes): lane l < count fills environment
@@ -103,9 +70,6 @@ __device__ __forceinline__ void ragged_planes_fill(const BatchParams<T> &p, T *b
 template <typename T, bool BOXES, bool REC>
 __global__ __launch_bounds__(BATCH_BLOCK) __attribute__((amdgpu_waves_per_eu(1, BOXES ? 1 : 8)))
 void ragged_step_kernel(BatchParams<T> p, Population pop) {
-    __shared__ Snap<T> s_snap[2][BATCH_BLOCK];
-    __shared__ int32_t s_fail[BATCH_BLOCK];      // per environment of the wave; sticky within a launch
-
     const int lane = threadIdx.x;
     const int M = p.M;
     // the plan: this lane's row (the grid is pop.waves workgroups of one wave)
@@ -123,151 +87,12 @@ void ragged_step_kernel(BatchParams<T> p, Population pop) {
     const int64_t env0 = pop.wave_env0[blockIdx.x];
     const int nenv = (int)(pop.wave_env0[blockIdx.x + 1] - env0);
 
-    // ---- load once ---------------------------------------------------------
     int32_t kind = 0;
     if constexpr (BOXES) kind = pop.kind[g];
-    const Snap<T> self = p.snap[g];
-    V3<T> x = {self.x, self.y, self.z};
-    const T bi = self.r;
-    Q4<T> q = {p.st.qw()[g], p.st.qx()[g], p.st.qy()[g], p.st.qz()[g]};
-    V3<T> v = {p.st.vx()[g], p.st.vy()[g], p.st.vz()[g]};
-    V3<T> w = {p.st.wx()[g], p.st.wy()[g], p.st.wz()[g]};
-    const T m = p.cs.mass()[g];
-    const V3<T> I = {p.cs.ix()[g], p.cs.iy()[g], p.cs.iz()[g]};
-    V3<T> sz = {p.cs.sx()[g], T(0), T(0)};
-    if constexpr (BOXES) {
-        const T sy = p.cs.sy()[g], szz = p.cs.sz()[g];
-        sz = {sz.x, kind != 0 ? sy : T(0), kind != 0 ? szz : T(0)};
-    }
-    // an environment that failed in an earlier launch is not advanced
-    bool failed = !active || p.code[env] != 0;
-    int32_t done = 0;
-
-    // the per-step constants solve_contact / apply_force read (rb_body.hpp)
-    StepParams<T> sp;
-    sp.xfrc = nullptr;
-    sp.rec_count = nullptr;
-    sp.S = 0;
-    batch_consts<T, true>(p, env, sp);
-    sp.thr = p.thr;
-    sp.oriented = p.oriented;
-
-    // ---- the environment's planes, the body's applied force -------------------
-    V3<T> xf = {T(0), T(0), T(0)}, xt = xf;
-    if (p.env_xfrc) {
-        const int64_t N = p.E * M;
-        xf = {p.env_xfrc[g], p.env_xfrc[N + g], p.env_xfrc[2 * N + g]};
-        xt = {p.env_xfrc[3 * N + g], p.env_xfrc[4 * N + g], p.env_xfrc[5 * N + g]};
-    }
-    T *blk = reinterpret_cast<T *>(s_env_dyn);
     const int stride = pop.epw_max;
-    ragged_planes_fill(p, blk, lane, env0, nenv, stride);   // (visible after the barrier below)
-    EnvPlanes<T> epl{};
-    epl.n_planes = p.n_planes;
-    epl.pn = {blk + el, stride};
-    epl.pp = {blk + 3 * stride + el, stride};
-
-    // the partners' constants, once per launch
-    T *poly = nullptr;
-    const Q4<T> *s_q = nullptr;
-    Q4<T> *s_qw = nullptr;
-    const T *s_e = nullptr;
-    const int32_t *s_k = nullptr;
-    if constexpr (BOXES) {
-        __shared__ Q4<T> s_quat[2 * BATCH_BLOCK];    // step-start orientations, beside s_snap: [2][BATCH_BLOCK]
-        __shared__ T s_ext[3 * BATCH_BLOCK];         // half extents (a sphere: its radius, 0, 0)
-        __shared__ int32_t s_kind[BATCH_BLOCK];
-        __shared__ T s_poly[48 * BATCH_BLOCK];       // box-box face clipping: 2 x 8 vertices x 3 per lane
-        s_kind[lane] = kind;
-        s_ext[lane] = sz.x; s_ext[BATCH_BLOCK + lane] = sz.y; s_ext[2 * BATCH_BLOCK + lane] = sz.z;
-        s_quat[lane] = q;
-        poly = s_poly + lane;
-        s_q = s_quat; s_qw = s_quat; s_e = s_ext; s_k = s_kind;
-    }
-    s_fail[lane] = 0;
-    s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
-    __syncthreads();
-
-    SampleTick tick = {p.phase, p.samp_first};
-
-    for (int s = 0; s < p.k; ++s) {
-        const Snap<T> *cur = s_snap[s & 1];
-        int32_t cx, cy, cz;
-        bool bad = !cell_of(x.x, x.y, x.z, p.inv_cs, cx, cy, cz);     // the step-start position
-
-        V3<T> vn = v, wn = w;
-        LazyInvI<T> invI;
-        invI.I = I;
-        invI.q = q;
-        // ---- a4: gravity; with forces set: the applied-force path ---------------
-        if (p.env_xfrc) apply_force(sp, m, invI, vn, wn, xf, xt);
-        else apply_force<T, false>(sp, 0, m, invI, vn, wn);
-        const T kk = impulse_k(m);
-
-        // ---- K2: plane contacts, plane order, by the lane's kind ---------------
-        int32_t nrec = 0;                        // (sp.rec_count is null: nothing is recorded)
-        [[maybe_unused]] M3<T> Mi;               // box orientation (the narrowphase below needs it too)
-        if constexpr (BOXES) {
-            if (kind != 0) Mi = mj_body_mat(q);
-            if (kind == 0) solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-            else solve_planes_box(sp, epl, 0, x, Mi, sz, m, kk, invI, vn, wn, nrec);
-        } else {
-            solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-        }
-
-        // ---- K2: every other present body of the environment, ascending id ------
-        for (int j = 0; j < nj; ++j) {
-            if (j == b) continue;
-            const Snap<T> sj = cur[ebase + j];
-            const V3<T> cj = {sj.x, sj.y, sj.z};
-            int32_t kj = 0;
-            if constexpr (BOXES) kj = s_k[ebase + j];
-            if (kind == 0 && kj == 0) {
-                if (!sphere_sphere_hit(x, sz.x, cj, sj.r)) continue;
-                solve_sphere_pair(sp, 0, b, j, x, sz.x, cj, sj.r, m, kk, invI, vn, wn, nrec);
-                continue;
-            }
-            if constexpr (BOXES) {
-                // box-involved: overlapping bounding spheres (candidate_hit, rb_step.hpp)
-                const V3<T> dd = {x.x - cj.x, x.y - cj.y, x.z - cj.z};
-                if (!(sqroot(mj_dot(dd, dd)) <= bi + sj.r)) continue;
-                const V3<T> hj = {s_e[ebase + j], s_e[BATCH_BLOCK + ebase + j], s_e[2 * BATCH_BLOCK + ebase + j]};
-                M3<T> Mj;
-                if (kj != 0) Mj = mj_body_mat(s_q[(s & 1) * BATCH_BLOCK + ebase + j]);
-                solve_box_pair(sp, 0, b, j, kind, kj, x, Mi, sz, cj, sj.r, Mj, hj, m, kk, invI, vn, wn, nrec, poly,
-                               BATCH_BLOCK);
-            }
-        }
-
-        // ---- K3: integrate (collision.py:90-100) ----------------------------
-        V3<T> xn = x;
-        Q4<T> qn;
-        integrate_pose(xn, qn, q, vn, wn, sp.dt);
-        bad = bad || !cell_of(xn.x, xn.y, xn.z, p.inv_cs, cx, cy, cz);
-
-        // a failing body fails its environment: none of its bodies advances
-        // (batch_step_kernel)
-        if (bad && active) s_fail[el] = 1;
-        s_snap[(s + 1) & 1][lane] = Snap<T>{xn.x, xn.y, xn.z, bi};
-        if constexpr (BOXES) s_qw[((s + 1) & 1) * BATCH_BLOCK + lane] = qn;   // every step: the partner of the next step may be new
-        __syncthreads();
-        failed = failed || s_fail[el] != 0;
-        if (!failed) {
-            x = xn; q = qn; v = vn; w = wn;
-            ++done;
-        }
-        if constexpr (REC) sample_tick(p, tick, active, g, x, q, v, w);
-    }
-
-    // ---- store once ------------------------------------------------------------
-    if (!active) return;
-    if (done > 0) {
-        p.snap[g] = Snap<T>{x.x, x.y, x.z, bi};
-        p.st.qw()[g] = q.w; p.st.qx()[g] = q.x; p.st.qy()[g] = q.y; p.st.qz()[g] = q.z;
-        p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
-        p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
-    }
-    batch_finish(p, b, env, done);
+    batch_step_body<T, BOXES, REC, true, BATCH_BLOCK>(p, active, g, env, b, ebase, nj, kind, el, stride, [&](T *blk) {
+        ragged_planes_fill(p, blk, lane, env0, nenv, stride);
+    });
 }
 
 // BLOCK: threads per workgroup, 64 * ceil(M / 64)
@@ -275,9 +100,6 @@ template <typename T, bool BOXES, bool REC, int BLOCK>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, BOXES ? 1 : 8)))
 void ragged_wide_kernel(BatchParams<T> p, Population pop) {
     static_assert(BLOCK % 64 == 0 && BLOCK > BATCH_BLOCK && BLOCK <= BATCH_WIDE_MAX, "one lane per body, whole waves");
-    __shared__ Snap<T> s_snap[2][BLOCK];
-    __shared__ int32_t s_fail[2];                // the workgroup's environment; word s & 1 is step s's (rb_batch_wide.hip)
-
     const int lane = threadIdx.x;                // = body id
     const int M = p.M;
     const int64_t env = blockIdx.x;              // (the grid is p.E workgroups)
@@ -289,148 +111,11 @@ void ragged_wide_kernel(BatchParams<T> p, Population pop) {
     const int64_t g = env * M + b;
     const int nj = active ? ne : 0;              // bodies whose pairs this lane evaluates
 
-    // ---- load once ---------------------------------------------------------
     int32_t kind = 0;
     if constexpr (BOXES) kind = pop.kind[g];
-    const Snap<T> self = p.snap[g];
-    V3<T> x = {self.x, self.y, self.z};
-    const T bi = self.r;
-    Q4<T> q = {p.st.qw()[g], p.st.qx()[g], p.st.qy()[g], p.st.qz()[g]};
-    V3<T> v = {p.st.vx()[g], p.st.vy()[g], p.st.vz()[g]};
-    V3<T> w = {p.st.wx()[g], p.st.wy()[g], p.st.wz()[g]};
-    const T m = p.cs.mass()[g];
-    const V3<T> I = {p.cs.ix()[g], p.cs.iy()[g], p.cs.iz()[g]};
-    V3<T> sz = {p.cs.sx()[g], T(0), T(0)};
-    if constexpr (BOXES) {
-        const T sy = p.cs.sy()[g], szz = p.cs.sz()[g];
-        sz = {sz.x, kind != 0 ? sy : T(0), kind != 0 ? szz : T(0)};
-    }
-    // an environment that failed in an earlier launch is not advanced
-    bool failed = !active || p.code[env] != 0;
-    int32_t done = 0;
-
-    // the per-step constants solve_contact / apply_force read (rb_body.hpp)
-    StepParams<T> sp;
-    sp.xfrc = nullptr;
-    sp.rec_count = nullptr;
-    sp.S = 0;
-    batch_consts<T, true>(p, env, sp);
-    sp.thr = p.thr;
-    sp.oriented = p.oriented;
-
-    // ---- the environment's planes, the body's applied force -------------------
-    V3<T> xf = {T(0), T(0), T(0)}, xt = xf;
-    if (p.env_xfrc) {
-        const int64_t N = p.E * M;
-        xf = {p.env_xfrc[g], p.env_xfrc[N + g], p.env_xfrc[2 * N + g]};
-        xt = {p.env_xfrc[3 * N + g], p.env_xfrc[4 * N + g], p.env_xfrc[5 * N + g]};
-    }
-    T *blk = reinterpret_cast<T *>(s_env_dyn);
-    ragged_planes_fill(p, blk, lane, env, 1, 1);     // one environment per block (visible after the barrier below)
-    EnvPlanes<T> epl{};
-    epl.n_planes = p.n_planes;
-    epl.pn = {blk, 1};
-    epl.pp = {blk + 3, 1};
-
-    // the partners' constants, once per launch
-    T *poly = nullptr;
-    const Q4<T> *s_q = nullptr;
-    Q4<T> *s_qw = nullptr;
-    const T *s_e = nullptr;
-    const int32_t *s_k = nullptr;
-    if constexpr (BOXES) {
-        __shared__ Q4<T> s_quat[2 * BLOCK];      // step-start orientations, beside s_snap: [2][BLOCK]
-        __shared__ T s_ext[3 * BLOCK];           // half extents (a sphere: its radius, 0, 0): [3][BLOCK]
-        __shared__ int32_t s_kind[BLOCK];
-        __shared__ T s_poly[48 * BLOCK];         // box-box face clipping: 2 x 8 vertices x 3 per lane
-        s_kind[lane] = kind;
-        s_ext[lane] = sz.x; s_ext[BLOCK + lane] = sz.y; s_ext[2 * BLOCK + lane] = sz.z;
-        s_quat[lane] = q;
-        poly = s_poly + lane;
-        s_q = s_quat; s_qw = s_quat; s_e = s_ext; s_k = s_kind;
-    }
-    if (lane < 2) s_fail[lane] = 0;
-    s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
-    __syncthreads();
-
-    SampleTick tick = {p.phase, p.samp_first};
-
-    for (int s = 0; s < p.k; ++s) {
-        const Snap<T> *cur = s_snap[s & 1];
-        int32_t cx, cy, cz;
-        bool bad = !cell_of(x.x, x.y, x.z, p.inv_cs, cx, cy, cz);     // the step-start position
-
-        V3<T> vn = v, wn = w;
-        LazyInvI<T> invI;
-        invI.I = I;
-        invI.q = q;
-        // ---- a4: gravity; with forces set: the applied-force path ---------------
-        if (p.env_xfrc) apply_force(sp, m, invI, vn, wn, xf, xt);
-        else apply_force<T, false>(sp, 0, m, invI, vn, wn);
-        const T kk = impulse_k(m);
-
-        // ---- K2: plane contacts, plane order, by the lane's kind ---------------
-        int32_t nrec = 0;                        // (sp.rec_count is null: nothing is recorded)
-        [[maybe_unused]] M3<T> Mi;               // box orientation (the narrowphase below needs it too)
-        if constexpr (BOXES) {
-            if (kind != 0) Mi = mj_body_mat(q);
-            if (kind == 0) solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-            else solve_planes_box(sp, epl, 0, x, Mi, sz, m, kk, invI, vn, wn, nrec);
-        } else {
-            solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-        }
-
-        // ---- K2: every other present body of the environment, ascending id ------
-        for (int j = 0; j < nj; ++j) {
-            if (j == b) continue;
-            const Snap<T> sj = cur[j];
-            const V3<T> cj = {sj.x, sj.y, sj.z};
-            int32_t kj = 0;
-            if constexpr (BOXES) kj = s_k[j];
-            if (kind == 0 && kj == 0) {
-                if (!sphere_sphere_hit(x, sz.x, cj, sj.r)) continue;
-                solve_sphere_pair(sp, 0, b, j, x, sz.x, cj, sj.r, m, kk, invI, vn, wn, nrec);
-                continue;
-            }
-            if constexpr (BOXES) {
-                // box-involved: overlapping bounding spheres (candidate_hit, rb_step.hpp)
-                const V3<T> dd = {x.x - cj.x, x.y - cj.y, x.z - cj.z};
-                if (!(sqroot(mj_dot(dd, dd)) <= bi + sj.r)) continue;
-                const V3<T> hj = {s_e[j], s_e[BLOCK + j], s_e[2 * BLOCK + j]};
-                M3<T> Mj;
-                if (kj != 0) Mj = mj_body_mat(s_q[(s & 1) * BLOCK + j]);
-                solve_box_pair(sp, 0, b, j, kind, kj, x, Mi, sz, cj, sj.r, Mj, hj, m, kk, invI, vn, wn, nrec, poly, BLOCK);
-            }
-        }
-
-        // ---- K3: integrate (collision.py:90-100) ----------------------------
-        V3<T> xn = x;
-        Q4<T> qn;
-        integrate_pose(xn, qn, q, vn, wn, sp.dt);
-        bad = bad || !cell_of(xn.x, xn.y, xn.z, p.inv_cs, cx, cy, cz);
-
-        // a failing body fails its environment: no body advances, in any wave
-        if (bad && active) s_fail[s & 1] = 1;
-        s_snap[(s + 1) & 1][lane] = Snap<T>{xn.x, xn.y, xn.z, bi};
-        if constexpr (BOXES) s_qw[((s + 1) & 1) * BLOCK + lane] = qn;   // every step: the partner of the next step may be new
-        __syncthreads();
-        failed = failed || s_fail[s & 1] != 0;
-        if (!failed) {
-            x = xn; q = qn; v = vn; w = wn;
-            ++done;
-        }
-        if constexpr (REC) sample_tick(p, tick, active, g, x, q, v, w);
-    }
-
-    // ---- store once ------------------------------------------------------------
-    if (!active) return;
-    if (done > 0) {
-        p.snap[g] = Snap<T>{x.x, x.y, x.z, bi};
-        p.st.qw()[g] = q.w; p.st.qx()[g] = q.x; p.st.qy()[g] = q.y; p.st.qz()[g] = q.z;
-        p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
-        p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
-    }
-    batch_finish(p, b, env, done);
+    // one environment per block: column 0 of a planes block of stride 1
+    batch_step_body<T, BOXES, REC, true, BLOCK>(p, active, g, env, b, 0, nj, kind, 0, 1,
+                                                [&](T *blk) { ragged_planes_fill(p, blk, lane, env, 1, 1); });
 }
 
 // ---- the contact query -----------------------------------------------------------
@@ -587,13 +272,6 @@ void ragged_wide_contacts_kernel(BatchParams<T> p, Population pop, ContactQuery 
     ragged_contacts_body<T, BOXES, BLOCK>(p, pop, q, in_range, blockIdx.x, in_range ? lane : 0, 0);
 }
 
-// the block of an environment of M bodies as a compile-time constant
-template <typename F> void with_block(int M, F &&f) {
-    if (M <= 128) f(std::integral_constant<int, 128>{});
-    else if (M <= 192) f(std::integral_constant<int, 192>{});
-    else f(std::integral_constant<int, 256>{});
-}
-
 bool pop_ok(const Population &pop, bool boxes, bool wide) {
     if (!pop.n_bodies || (boxes && !pop.kind)) return false;
     return wide || (pop.wave_env0 && pop.lane_row && pop.waves >= 1 && pop.epw_max >= 1 && pop.epw_max <= BATCH_BLOCK);
@@ -607,8 +285,7 @@ hipError_t launch_ragged_step(const BatchParams<T> &p, const Population &pop, bo
     if (p.M < 1 || p.M > BATCH_WIDE_MAX || p.n_planes < 0 || p.n_planes > MAX_PLANES) return hipErrorInvalidValue;
     const bool wide = p.M > BATCH_BLOCK;
     if (!pop_ok(pop, boxes, wide)) return hipErrorInvalidValue;
-    if (rec && (!p.samp || p.every < 1 || p.phase < 1 || p.phase > p.every || (p.samp_rows != 7 && p.samp_rows != 13)))
-        return hipErrorInvalidValue;
+    if (rec && !rec_ok(p)) return hipErrorInvalidValue;
     as_constant(boxes, [&](auto BOXES) {
         as_constant(rec, [&](auto REC) {
             if (wide) {
@@ -633,11 +310,7 @@ template <typename T>
 hipError_t launch_ragged_contacts(const BatchParams<T> &p, const Population &pop, const ContactQuery &q, bool boxes,
                                   hipStream_t s) {
     if (q.n <= 0) return hipSuccess;
-    if (p.M < 1 || p.M > BATCH_WIDE_MAX || p.n_planes < 0 || p.n_planes > MAX_PLANES || q.R < 0 || !q.counts)
-        return hipErrorInvalidValue;
-    if (q.R > 0 && (!q.partner || !q.kind || !q.dist)) return hipErrorInvalidValue;
-    if (!pop_ok(pop, boxes, true)) return hipErrorInvalidValue;
-    if (!q.ids && (q.env0 < 0 || q.env0 + q.n > p.E)) return hipErrorInvalidValue;
+    if (!query_ok(p, q, 1, BATCH_WIDE_MAX) || !pop_ok(pop, boxes, true)) return hipErrorInvalidValue;
     as_constant(boxes, [&](auto BOXES) {
         if (p.M > BATCH_BLOCK) {
             with_block(p.M, [&](auto BLOCK) {

@@ -8,14 +8,14 @@
 // slot 0's data, visit no partner, store nothing and raise no failure, and
 // they reach every barrier (nothing returns before the step loop ends).
 //
-// A step is batch_mixed_kernel's (BOXES; rb_batch_boxes.hip) or
-// batch_step_kernel's sphere path (!BOXES; rb_batch.hip), from the same
-// functions (rb_body.hpp, rb_device.hpp, rb_boxes.hpp) in the same frame
-// (rb_batch_frame.hpp): partners in ascending id over the whole environment,
-// step-start snapshots (BOXES: orientations too) ping-pong in LDS, one
-// __syncthreads() per step, state in registers for up to RB_BATCH_CHUNK steps.
-// So an environment steps bit-identically to a world of its scene, whichever
-// waves its bodies sit in.
+// A step is batch_step_body (rb_batch_body.hpp), one text for this unit's and
+// rb_batch_ragged.hip's step kernels: batch_mixed_kernel's sequence (BOXES) or
+// batch_step_kernel's sphere path (!BOXES; rb_batch.hip), partners in
+// ascending id over the whole environment, step-start snapshots (BOXES:
+// orientations too) ping-pong in LDS, one __syncthreads() per step, state in
+// registers for up to RB_BATCH_CHUNK steps.  So an environment steps
+// bit-identically to a world of its scene, whichever waves its bodies sit in.
+// The kernel below is the mapping alone.
 //
 // What the workgroup barrier changes against the one-wave kernels is the
 // failure flag.  Waves leave a barrier at different times: a wave that is
@@ -24,54 +24,18 @@
 // therefore ping-pongs as the snapshots do: step s raises and reads word
 // s & 1, which nobody writes again before the barrier of step s + 1.  A word
 // is never cleared: once it is read as set every lane is failed for good.
+// (batch_step_body does this for every block of more than one wave.)
 //
 // LDS scales with the block (a template parameter): BOXES at f64 takes 69,128 /
 // 103,688 / 138,248 bytes at 128 / 192 / 256 threads, of which the clipping
 // polygon (a column of 48 reals per lane, stride BLOCK) is 48 * BLOCK * 8.
 // BOXES is built as batch_mixed_kernel is: one wave per SIMD.
 // Built once per real type: RB_INST = 1 fp64, 2 fp32.
-#include "rb_device.hpp"
-#include "rb_grid.hpp"
-#include "rb_internal.hpp"
-#include "rb_body.hpp"
-#include "rb_boxes.hpp"
-#include "rb_batch_frame.hpp"
-#include "rb_batch_contacts.hpp"
+#include "rb_batch_body.hpp"
 #include "rb_contacts.hpp"
 
 namespace rb {
 namespace {
-
-// solve_box_pair of rb_batch_boxes.hip, a second copy of its text: that unit's
-// kernels are pinned to the code they compile to, and sharing the function
-// through a header would have to be proven neutral there by a resource listing
-// and an interleaved run of the existing path; the copy leaves that unit's
-// text untouched.  (Anonymous namespace: no symbol of that unit is redefined.)
-template <typename T>
-__device__ __forceinline__ void solve_box_pair(const StepParams<T> &p, int32_t l, int32_t i, int32_t j, int32_t kind,
-                                               int32_t kj, V3<T> x, const M3<T> &M, V3<T> sz, V3<T> cj, T rj,
-                                               const M3<T> &Mj, V3<T> hj, T m, T k, LazyInvI<T> &invI, V3<T> &v,
-                                               V3<T> &w, int32_t &nrec, T *poly, int ps) {
-    auto emit = [&](const Contact<T> &con, int ck, bool self_g1) {
-        record(p, l, nrec, j, ck, con.dist);
-        const V3<T> n = (p.oriented && self_g1) ? V3<T>{-con.frame.x, -con.frame.y, -con.frame.z} : con.frame;
-        solve_contact(p, con, x, n, m, k, invI, v, w);
-    };
-    // geom1: the sphere of a sphere-box pair, else the lower id
-    // (one call of each primitive, operands selected)
-    const bool g1 = (kind == 0 && kj != 0) || (kind != 0 && kj != 0 && i < j);
-    const V3<T> p1 = g1 ? x : cj, p2 = g1 ? cj : x;
-    const V3<T> h1 = g1 ? sz : hj, h2 = g1 ? hj : sz;
-    M3<T> M1, M2;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) { M1.a[c] = g1 ? M.a[c] : Mj.a[c]; M2.a[c] = g1 ? Mj.a[c] : M.a[c]; }
-    if (kind == 0 || kj == 0) {
-        Contact<T> con;
-        if (sphere_box(p1, g1 ? sz.x : rj, p2, M2, h2, con)) emit(con, CK_SPHERE_BOX, g1);
-    } else {
-        box_box(p1, M1, h1, p2, M2, h2, poly, ps, [&](const Contact<T> &c, int ck) { emit(c, ck, g1); });
-    }
-}
 
 // BOXES: the template holds a box (a lane's kind is the template's kind of its
 // body); else spheres only: no polygon, orientation, extent or kind LDS
@@ -82,9 +46,6 @@ template <typename T, bool BOXES, bool REC, bool ENVS, int BLOCK>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, BOXES ? 1 : 8)))
 void batch_wide_kernel(BatchParams<T> p) {
     static_assert(BLOCK % 64 == 0 && BLOCK > BATCH_BLOCK && BLOCK <= BATCH_WIDE_MAX, "one lane per body, whole waves");
-    __shared__ Snap<T> s_snap[2][BLOCK];
-    __shared__ int32_t s_fail[2];                // the workgroup's environment; word s & 1 is step s's (see above)
-
     const int lane = threadIdx.x;                // = body id
     const int M = p.M;
     // idle lanes run along on slot 0's data, visit no partner and store nothing
@@ -94,156 +55,11 @@ void batch_wide_kernel(BatchParams<T> p) {
     const int64_t g = active ? env * M + b : 0;
     const int nj = active ? M : 0;               // bodies whose pairs this lane evaluates
 
-    // ---- load once ---------------------------------------------------------
     int32_t kind = 0;
     if constexpr (BOXES) kind = p.cs.kind[b];            // [M]: the template's kinds
-    const Snap<T> self = p.snap[g];
-    V3<T> x = {self.x, self.y, self.z};
-    const T bi = self.r;
-    Q4<T> q = {p.st.qw()[g], p.st.qx()[g], p.st.qy()[g], p.st.qz()[g]};
-    V3<T> v = {p.st.vx()[g], p.st.vy()[g], p.st.vz()[g]};
-    V3<T> w = {p.st.wx()[g], p.st.wy()[g], p.st.wz()[g]};
-    const T m = p.cs.mass()[g];
-    const V3<T> I = {p.cs.ix()[g], p.cs.iy()[g], p.cs.iz()[g]};
-    V3<T> sz = {p.cs.sx()[g], T(0), T(0)};
-    if constexpr (BOXES) {
-        const T sy = p.cs.sy()[g], szz = p.cs.sz()[g];
-        sz = {sz.x, kind != 0 ? sy : T(0), kind != 0 ? szz : T(0)};
-    }
-    // an environment that failed in an earlier launch is not advanced
-    bool failed = !active || p.code[env] != 0;
-    int32_t done = 0;
-
-    // the per-step constants solve_contact / apply_force read (rb_body.hpp)
-    StepParams<T> sp;
-    sp.xfrc = nullptr;
-    sp.rec_count = nullptr;
-    sp.S = 0;
-    batch_consts<T, ENVS>(p, env, sp);
-    sp.thr = p.thr;
-    sp.oriented = p.oriented;
-
-    // ---- ENVS: the environment's planes, the body's applied force -----------
-    V3<T> xf = {T(0), T(0), T(0)}, xt = xf;
-    EnvPlanes<T> epl{};
-    if constexpr (ENVS) {
-        if (p.env_xfrc) {
-            const int64_t N = p.E * M;
-            xf = {p.env_xfrc[g], p.env_xfrc[N + g], p.env_xfrc[2 * N + g]};
-            xt = {p.env_xfrc[3 * N + g], p.env_xfrc[4 * N + g], p.env_xfrc[5 * N + g]};
-        }
-        T *blk = reinterpret_cast<T *>(s_env_dyn);
-        env_planes_fill(p, blk, lane, 1);            // one environment per block (visible after the barrier below)
-        epl.n_planes = p.n_planes;
-        epl.pn = {blk, 1};
-        epl.pp = {blk + 3, 1};
-    }
-
-    // the partners' constants, once per launch
-    T *poly = nullptr;
-    const Q4<T> *s_q = nullptr;
-    Q4<T> *s_qw = nullptr;
-    const T *s_e = nullptr;
-    const int32_t *s_k = nullptr;
-    if constexpr (BOXES) {
-        __shared__ Q4<T> s_quat[2 * BLOCK];      // step-start orientations, beside s_snap: [2][BLOCK]
-        __shared__ T s_ext[3 * BLOCK];           // half extents (a sphere: its radius, 0, 0): [3][BLOCK]
-        __shared__ int32_t s_kind[BLOCK];
-        __shared__ T s_poly[48 * BLOCK];         // box-box face clipping: 2 x 8 vertices x 3 per lane
-        s_kind[lane] = kind;
-        s_ext[lane] = sz.x; s_ext[BLOCK + lane] = sz.y; s_ext[2 * BLOCK + lane] = sz.z;
-        s_quat[lane] = q;
-        poly = s_poly + lane;
-        s_q = s_quat; s_qw = s_quat; s_e = s_ext; s_k = s_kind;
-    }
-    if (lane < 2) s_fail[lane] = 0;
-    s_snap[0][lane] = Snap<T>{x.x, x.y, x.z, bi};
-    __syncthreads();
-
-    SampleTick tick = {p.phase, p.samp_first};
-
-    for (int s = 0; s < p.k; ++s) {
-        const Snap<T> *cur = s_snap[s & 1];
-        int32_t cx, cy, cz;
-        bool bad = !cell_of(x.x, x.y, x.z, p.inv_cs, cx, cy, cz);     // the step-start position
-
-        V3<T> vn = v, wn = w;
-        LazyInvI<T> invI;
-        invI.I = I;
-        invI.q = q;
-        // ---- a4: gravity; ENVS with forces set: the applied-force path ---------
-        if (ENVS && p.env_xfrc) apply_force(sp, m, invI, vn, wn, xf, xt);
-        else apply_force<T, false>(sp, 0, m, invI, vn, wn);
-        const T kk = impulse_k(m);
-
-        // ---- K2: plane contacts, plane order, by the lane's kind ---------------
-        int32_t nrec = 0;                        // (sp.rec_count is null: nothing is recorded)
-        [[maybe_unused]] M3<T> Mi;               // box orientation (the narrowphase below needs it too)
-        if constexpr (BOXES) {
-            if (kind != 0) Mi = mj_body_mat(q);
-            if constexpr (ENVS) {
-                if (kind == 0) solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-                else solve_planes_box(sp, epl, 0, x, Mi, sz, m, kk, invI, vn, wn, nrec);
-            } else {
-                if (kind == 0) solve_planes_sphere(sp, p, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-                else solve_planes_box(sp, p, 0, x, Mi, sz, m, kk, invI, vn, wn, nrec);
-            }
-        } else {
-            if constexpr (ENVS) solve_planes_sphere(sp, epl, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-            else solve_planes_sphere(sp, p, 0, x, sz.x, m, kk, invI, vn, wn, nrec);
-        }
-
-        // ---- K2: every other body of the environment, ascending id ----------
-        for (int j = 0; j < nj; ++j) {
-            if (j == b) continue;
-            const Snap<T> sj = cur[j];
-            const V3<T> cj = {sj.x, sj.y, sj.z};
-            int32_t kj = 0;
-            if constexpr (BOXES) kj = s_k[j];
-            if (kind == 0 && kj == 0) {
-                if (!sphere_sphere_hit(x, sz.x, cj, sj.r)) continue;
-                solve_sphere_pair(sp, 0, b, j, x, sz.x, cj, sj.r, m, kk, invI, vn, wn, nrec);
-                continue;
-            }
-            if constexpr (BOXES) {
-                // box-involved: overlapping bounding spheres (candidate_hit, rb_step.hpp)
-                const V3<T> dd = {x.x - cj.x, x.y - cj.y, x.z - cj.z};
-                if (!(sqroot(mj_dot(dd, dd)) <= bi + sj.r)) continue;
-                const V3<T> hj = {s_e[j], s_e[BLOCK + j], s_e[2 * BLOCK + j]};
-                M3<T> Mj;
-                if (kj != 0) Mj = mj_body_mat(s_q[(s & 1) * BLOCK + j]);
-                solve_box_pair(sp, 0, b, j, kind, kj, x, Mi, sz, cj, sj.r, Mj, hj, m, kk, invI, vn, wn, nrec, poly, BLOCK);
-            }
-        }
-
-        // ---- K3: integrate (collision.py:90-100) ----------------------------
-        V3<T> xn = x;
-        Q4<T> qn;
-        integrate_pose(xn, qn, q, vn, wn, sp.dt);
-        bad = bad || !cell_of(xn.x, xn.y, xn.z, p.inv_cs, cx, cy, cz);
-
-        // a failing body fails its environment: no body advances, in any wave
-        if (bad && active) s_fail[s & 1] = 1;
-        s_snap[(s + 1) & 1][lane] = Snap<T>{xn.x, xn.y, xn.z, bi};
-        if constexpr (BOXES) s_qw[((s + 1) & 1) * BLOCK + lane] = qn;   // every step: the partner of the next step may be new
-        __syncthreads();
-        failed = failed || s_fail[s & 1] != 0;
-        if (!failed) {
-            x = xn; q = qn; v = vn; w = wn;
-            ++done;
-        }
-        if constexpr (REC) sample_tick(p, tick, active, g, x, q, v, w);
-    }
-
-    // ---- store once ------------------------------------------------------------
-    if (!active) return;
-    if (done > 0) {
-        p.snap[g] = Snap<T>{x.x, x.y, x.z, bi};
-        p.st.qw()[g] = q.w; p.st.qx()[g] = q.x; p.st.qy()[g] = q.y; p.st.qz()[g] = q.z;
-        p.st.vx()[g] = v.x; p.st.vy()[g] = v.y; p.st.vz()[g] = v.z;
-        p.st.wx()[g] = w.x; p.st.wy()[g] = w.y; p.st.wz()[g] = w.z;
-    }
-    batch_finish(p, b, env, done);
+    // one environment per block: column 0 of a planes block of stride 1
+    batch_step_body<T, BOXES, REC, ENVS, BLOCK>(p, active, g, env, b, 0, nj, kind, 0, 1,
+                                                [&](T *blk) { env_planes_fill(p, blk, lane, 1); });
 }
 
 // ---- the contact query of a wide batch ------------------------------------------
@@ -376,21 +192,13 @@ void wide_contacts_kernel(BatchParams<T> p, ContactQuery q) {
     for (int32_t s = failed ? 0 : n; s < R; ++s) put_record(q, slot0 + s, 0, -1, T(0), zero, zero);
 }
 
-// the block of an environment of M bodies as a compile-time constant
-template <typename F> void with_block(int M, F &&f) {
-    if (M <= 128) f(std::integral_constant<int, 128>{});
-    else if (M <= 192) f(std::integral_constant<int, 192>{});
-    else f(std::integral_constant<int, 256>{});
-}
-
 }  // namespace
 
 template <typename T> hipError_t launch_batch_wide(const BatchParams<T> &p, bool boxes, bool rec, hipStream_t s) {
     if (p.E <= 0 || p.k <= 0) return hipSuccess;
     if (p.M <= BATCH_BLOCK || p.M > BATCH_WIDE_MAX || p.n_planes < 0 || p.n_planes > MAX_PLANES) return hipErrorInvalidValue;
     if (boxes && !p.cs.kind) return hipErrorInvalidValue;
-    if (rec && (!p.samp || p.every < 1 || p.phase < 1 || p.phase > p.every || (p.samp_rows != 7 && p.samp_rows != 13)))
-        return hipErrorInvalidValue;
+    if (rec && !rec_ok(p)) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)p.E;       // one environment per workgroup
     with_block(p.M, [&](auto BLOCK) {
         as_constant(boxes, [&](auto BOXES) {
@@ -410,11 +218,7 @@ template <typename T> hipError_t launch_batch_wide(const BatchParams<T> &p, bool
 template <typename T>
 hipError_t launch_batch_wide_contacts(const BatchParams<T> &p, const ContactQuery &q, bool boxes, hipStream_t s) {
     if (q.n <= 0) return hipSuccess;
-    if (p.M <= BATCH_BLOCK || p.M > BATCH_WIDE_MAX || p.n_planes < 0 || p.n_planes > MAX_PLANES || q.R < 0 || !q.counts)
-        return hipErrorInvalidValue;
-    if (q.R > 0 && (!q.partner || !q.kind || !q.dist)) return hipErrorInvalidValue;
-    if (boxes && !p.cs.kind) return hipErrorInvalidValue;
-    if (!q.ids && (q.env0 < 0 || q.env0 + q.n > p.E)) return hipErrorInvalidValue;
+    if (!query_ok(p, q, BATCH_BLOCK + 1, BATCH_WIDE_MAX) || (boxes && !p.cs.kind)) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)q.n;       // one row per workgroup
     with_block(p.M, [&](auto BLOCK) {
         as_constant(boxes, [&](auto BOXES) {

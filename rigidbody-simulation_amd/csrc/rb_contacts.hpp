@@ -4,12 +4,15 @@
 // and the emission of one pair as the world's query runs them.
 //
 // The batch kernels keep the walk and the pair emission in line
-// (contacts_body, wide_contacts_kernel): moved onto contacts_planes /
-// contacts_pair below they produce the same lists with other register counts
-// (profiles/world_contacts/pair_share_resources.txt), and those kernels are
-// not this header's to change.  The order, the geom1 rule and the tests are
-// the same text in both places; tests/test_gpu_world_contacts.py holds the
-// world's lists equal to the batch's word for word.
+// (contacts_body, wide_contacts_kernel, ragged_contacts_body).  Moved onto one
+// body built on contacts_planes / contacts_pair below they produce the same
+// lists in fewer registers (the box instances 232 -> 181 at f64, 162 -> 134 at
+// f32), and the mixed template's query of 1,024 environments took 32.6-33.4 us
+// a call against 31.9-32.2 in an alternating run, so they stay as they are
+// (cause not found; DESIGN 4.3, profiles/batch_unify).  The order, the geom1
+// rule and the tests are the same text in all four places;
+// tests/test_gpu_world_contacts.py holds the world's lists equal to the
+// batch's word for word.
 // Device code only.
 #pragma once
 
