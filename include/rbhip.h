@@ -449,7 +449,8 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * under either contact law (rb_batch_set_contact_law).
  * Arrays are environment-major: body k of environment e at row e*M + k.
  * Not covered (use rb_world): contacts recorded inside a step (a batch is
- * asked for the contact list of its current state: rb_batch_contacts), sharding,
+ * asked for the contact list of its current state: rb_batch_contacts, and for
+ * the impulses of its next step: rb_batch_impulses), sharding,
  * per-environment plane counts, more than 256 bodies per
  * environment; under RB_LAW_BALLS also per-environment planes, applied
  * forces, the contact query, environments of more than 64 bodies and
@@ -758,6 +759,83 @@ int  rb_batch_contacts(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t m
  * from the batch's real type by a C cast. */
 int  rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, int32_t *partner,
                            int32_t *kind, void *dist, void *pos, void *frame, int32_t io_dtype);
+
+/* ---- the impulse query of a batch (additive to librbhip 0.4) -------------------
+ * What the next rb_batch_step(1, dt, restitution, friction, contact_threshold)
+ * does to every body, contact by contact: the two return values jn and jt of
+ * compute_collision_impulse_friction (collision.py:7-48) for every contact of
+ * the per-body Gauss-Seidel loop (collision.py:72-88), the velocity that
+ * apply_impulse_friction (physics_utils.py:25-49) leaves behind, and the body's
+ * net contact impulse.  The reference computes jn and jt and drops them; this
+ * call replaces reading them out of those call sites.  A pure function of the
+ * batch's current state, the step parameters of the call and the batch's
+ * constants: it steps nothing, fails nothing (the position check of a step is
+ * not run) and changes nothing.
+ *
+ * Layout: rb_batch_contacts', dense, R = max_records slots per body.  counts
+ * [n][M]; partner, kind, dist and jn [n][M][R]; jt [n][M][R][3]; vel and net
+ * [n][M][6].
+ *
+ * counts, partner, kind and dist are word for word what rb_batch_contacts
+ * writes for the same state and the same R: the same canonical order (geom1
+ * as defined there), the true count past R, kind -1 and zeros in the unused
+ * slots (in jn and jt as well), count -1 for every body of a failed
+ * environment, count 0 for an absent body of a population.
+ *
+ * jn, jt: the solve visits the contacts of a body in list order, from the
+ * velocity that gravity, the applied forces and the earlier contacts of this
+ * body have left.  A contact the step skips (dist not below 0, or |dist| <
+ * contact_threshold) has jn 0 and jt 0; so has a separating one (u_rel_n >= 0),
+ * as the reference function returns it.  The normal is the step's: the frame
+ * flipped for the geom1 body under RB_NORMAL_ORIENTED, raw under RB_NORMAL_RAW.
+ *
+ * vel: (v, omega) of the body after gravity, applied forces and all its
+ * contacts: for every environment the step commits, the words
+ * rb_batch_step(1, ...) writes into qvel.
+ * net: the body's net contact impulse and net angular impulse about its
+ * centre, sum of P and sum of r x P over its applied contacts in list order
+ * from +0, P = jn n + jt as apply_impulse_friction evaluates it; gravity and
+ * applied forces are not part of it.  net[0:3] / dt is the average contact
+ * force of the step.
+ * Truncation drops records only: the solve runs over every contact, vel and
+ * net do not depend on R.  The vel and net rows of failed environments and of
+ * absent bodies are zeros.
+ *
+ * restitution and friction are the scalars of the call unless
+ * rb_batch_set_params set per-environment values; per-environment planes,
+ * gravity and applied forces are honoured as the step honours them (the
+ * applied-force path for all-zero rows once forces are set), and so is a
+ * population.
+ *
+ * counts is required.  partner, kind, dist, jn and jt are given all together
+ * with R > 0, or are all NULL with R 0 (the cheap "sensor only" call).  vel and
+ * net may each be NULL.
+ *
+ * RB_EINVAL, with nothing enqueued: every case of rb_batch_contacts; what
+ * rb_batch_step refuses (dt not positive, a negative restitution, friction or
+ * contact_threshold, NaN); a non-finite dt, restitution, friction or
+ * contact_threshold.  RB_EUNSUPPORTED under RB_LAW_BALLS.
+ *
+ * rb_batch_impulses: host arrays, the listed environments, synchronous (it
+ * finishes the batch's pending work first), staged in rb_batch_contacts'
+ * buffer under RBHIP_BATCH_SAMPLE_BYTES and cut into launches over ranges of
+ * the listed environments alike (RB_EINVAL if one environment alone does not
+ * fit).  *n_truncated (may be NULL) = the listed bodies with count > R.
+ * rb_batch_impulses_dev: device arrays of the caller, all environments,
+ * enqueued on the batch's stream without waiting; pointers are checked on the
+ * host; reals are of io_dtype, converted by a C cast.  Not offered under a
+ * stream capture.
+ *
+ * Not covered: the same query for an rb_world; impulses recorded inside
+ * rb_batch_run_sampled; the two-ball law. */
+int  rb_batch_impulses(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t max_records,
+                       double dt, double restitution, double friction, double contact_threshold,
+                       int32_t *counts, int32_t *partner, int32_t *kind, double *dist,
+                       double *jn, double *jt, double *vel, double *net, int64_t *n_truncated);
+int  rb_batch_impulses_dev(rb_batch *b, int32_t max_records,
+                           double dt, double restitution, double friction, double contact_threshold,
+                           int32_t *counts, int32_t *partner, int32_t *kind, void *dist,
+                           void *jn, void *jt, void *vel, void *net, int32_t io_dtype);
 
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do

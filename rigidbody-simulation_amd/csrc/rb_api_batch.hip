@@ -11,6 +11,7 @@
 
 #include "rb_batch_contacts.hpp"
 #include "rb_batch_dev.hpp"
+#include "rb_batch_impulses.hpp"
 #include "rb_batch_ragged.hpp"
 #include "rb_host.hpp"
 #include "rb_laneplan.hpp"
@@ -502,6 +503,97 @@ int batch_launch_contacts(rb_batch *b, const ContactQuery &q) {
     return RB_OK;
 }
 
+// ---- what the host forms of the queries share (rb_batch_contacts, rb_batch_impulses) ----
+// the listed environments of a host form: n of them, in range, none twice
+int batch_check_query_ids(const rb_batch *b, const int64_t *env_ids, int64_t n) {
+    if (n < 0) return fail(RB_EINVAL, "n < 0");
+    WCHK(batch_check_ids(b, env_ids, n));
+    if (env_ids) {
+        std::vector<int64_t> sorted(env_ids, env_ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return fail(RB_EINVAL, "env_ids lists environment %lld twice", (long long)*dup);
+    }
+    return RB_OK;
+}
+
+// Does one listed environment (`per` bytes of `what`) fit the staging buffer?  (Before any device call.)
+int batch_check_query_fit(const rb_batch *b, size_t per, const char *what) {
+    if (per > b->samp_limit)
+        return fail(RB_EINVAL, "%s of one environment (%zu bytes) do not fit the staging buffer (%zu bytes: "
+                               "RBHIP_BATCH_SAMPLE_BYTES)", what, per, b->samp_limit);
+    return RB_OK;
+}
+
+// The host form of a query over n >= 1 listed environments of `per` bytes each
+// in the staging buffer (b->con; it only grows, at most samp_limit bytes): the
+// ids onto the device, then a range of listed environments per launch.
+// range(first, c) enqueues the launch and the downloads of the c environments
+// from `first` on; the stream is waited for after each range, since the next
+// one reuses the buffer.
+template <typename F> int batch_query_ranges(rb_batch *b, const int64_t *env_ids, int64_t n, size_t per, F &&range) {
+    const int64_t fit = std::min<int64_t>(n, (int64_t)(b->samp_limit / per));
+    HIPCHK(hipSetDevice(b->device));
+    if (per * (size_t)fit > b->con_bytes) {
+        if (b->con) { HIPCHK(hipFree(b->con)); b->con = nullptr; }
+        b->con_bytes = 0;
+        HIPCHK(hipMalloc((void **)&b->con, per * (size_t)fit));
+        b->con_bytes = per * (size_t)fit;
+    }
+    if (env_ids) WCHK(batch_put_ids(b, env_ids, n));
+    for (int64_t first = 0; first < n; first += fit) {
+        WCHK(range(first, (size_t)std::min<int64_t>(fit, n - first)));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return RB_OK;
+}
+
+// a download of a range into the caller's array, on the batch's stream
+hipError_t batch_get(rb_batch *b, void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
+}
+
+// the bodies whose true count is past R
+int64_t batch_truncated(const int32_t *counts, size_t bodies, int32_t R) {
+    int64_t t = 0;
+    for (size_t k = 0; k < bodies; ++k) t += counts[k] > R;
+    return t;
+}
+
+// every array of a device form that is given: device memory of the batch's device
+int batch_dev_ptrs(const rb_batch *b, std::initializer_list<std::pair<const void *, const char *>> arrays) {
+    for (const auto &a : arrays)
+        if (a.first) WCHK(batch_dev_ptr(b, a.first, a.second));
+    return RB_OK;
+}
+
+// ---- the impulse query (rb_batch_impulses, rb_batch_impulses_dev) ----------------
+// the arguments both forms share, before any device call: the contact query's
+// (jn and jt with the records), rb_batch_step's parameters, finite
+int batch_check_impulses(const rb_batch *b, int32_t R, const void *counts, const void *partner, const void *kind,
+                         const void *dist, const void *jn, const void *jt, double dt, double e, double mu, double thr) {
+    WCHK(batch_check_contacts(b, R, counts, partner, kind, dist, nullptr, nullptr));
+    if ((jn != nullptr) != (partner != nullptr) || (jt != nullptr) != (partner != nullptr))
+        return fail(RB_EINVAL, "partner, kind, dist, jn and jt may be NULL only all together (max_records 0)");
+    WCHK(batch_check_step(b, 1, dt, e, mu, thr));
+    if (!std::isfinite(dt) || !std::isfinite(e) || !std::isfinite(mu) || !std::isfinite(thr))
+        return fail(RB_EINVAL, "non-finite step parameters dt=%g e=%g mu=%g thr=%g", dt, e, mu, thr);
+    return RB_OK;
+}
+
+// one launch of the query: rows [0, q.c.n) of q, by the batch's kind
+int batch_launch_impulses(rb_batch *b, ImpulseQuery q, double dt, double e, double mu, double thr) {
+    // (with a population the kinds are the population's: no one-box instance)
+    q.c.box = b->box && !b->pop_set;
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        const BatchParams<T> p = batch_params<T>(b, 1, dt, e, mu, thr);
+        if (b->pop_set) return launch_batch_impulses<T>(p, batch_population(b), q, b->pop_boxes, b->stream);
+        return launch_batch_impulses<T>(p, Population{}, q, b->mixed, b->stream);
+    }));
+    return RB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -975,35 +1067,16 @@ int rb_batch_contacts(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t ma
     ApiScope api_scope_(b ? b->device : -1);
     const int32_t R = max_records;
     WCHK(batch_check_contacts(b, R, counts, partner, kind, dist, pos, frame));
-    if (n < 0) return fail(RB_EINVAL, "n < 0");
-    WCHK(batch_check_ids(b, env_ids, n));
-    if (env_ids) {
-        std::vector<int64_t> sorted(env_ids, env_ids + n);
-        std::sort(sorted.begin(), sorted.end());
-        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
-        if (dup != sorted.end()) return fail(RB_EINVAL, "env_ids lists environment %lld twice", (long long)*dup);
-    }
+    WCHK(batch_check_query_ids(b, env_ids, n));
     WCHK(batch_check_contact_law(b));
     if (n_truncated) *n_truncated = 0;
     if (n == 0) return RB_OK;
     // one listed environment in the staging buffer: the reals first (aligned), then the words
     const size_t M = (size_t)b->M, MR = M * (size_t)R;
     const size_t per = sizeof(double) * MR * (1 + (pos ? 3 : 0) + (frame ? 3 : 0)) + sizeof(int32_t) * (M + 2 * MR);
-    if (per > b->samp_limit)
-        return fail(RB_EINVAL, "the contact lists of one environment (%zu bytes) do not fit the staging buffer (%zu bytes: "
-                               "RBHIP_BATCH_SAMPLE_BYTES)", per, b->samp_limit);
-    const int64_t fit = std::min<int64_t>(n, (int64_t)(b->samp_limit / per));
-    HIPCHK(hipSetDevice(b->device));
-    if (per * (size_t)fit > b->con_bytes) {
-        if (b->con) { HIPCHK(hipFree(b->con)); b->con = nullptr; }
-        b->con_bytes = 0;
-        HIPCHK(hipMalloc((void **)&b->con, per * (size_t)fit));
-        b->con_bytes = per * (size_t)fit;
-    }
-    if (env_ids) WCHK(batch_put_ids(b, env_ids, n));
-    // a range of listed environments per launch
-    for (int64_t first = 0; first < n; first += fit) {
-        const size_t c = (size_t)std::min<int64_t>(fit, n - first), at = (size_t)first;
+    WCHK(batch_check_query_fit(b, per, "the contact lists"));
+    WCHK(batch_query_ranges(b, env_ids, n, per, [&](int64_t first, size_t c) {
+        const size_t at = (size_t)first;
         double *d_dist = reinterpret_cast<double *>(b->con);
         double *d_pos = d_dist + c * MR, *d_frame = d_pos + (pos ? 3 * c * MR : 0);
         int32_t *d_counts = reinterpret_cast<int32_t *>(d_frame + (frame ? 3 * c * MR : 0));
@@ -1020,24 +1093,17 @@ int rb_batch_contacts(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t ma
         q.io32 = 0;
         q.box = b->box;
         WCHK(batch_launch_contacts(b, q));
-        const auto get = [&](void *dst, const void *src, size_t bytes) {
-            return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
-        };
-        HIPCHK(get(counts + at * M, d_counts, sizeof(int32_t) * c * M));
+        HIPCHK(batch_get(b, counts + at * M, d_counts, sizeof(int32_t) * c * M));
         if (R > 0) {
-            HIPCHK(get(partner + at * MR, d_partner, sizeof(int32_t) * c * MR));
-            HIPCHK(get(kind + at * MR, d_kind, sizeof(int32_t) * c * MR));
-            HIPCHK(get(dist + at * MR, d_dist, sizeof(double) * c * MR));
-            if (pos) HIPCHK(get(pos + 3 * at * MR, d_pos, sizeof(double) * 3 * c * MR));
-            if (frame) HIPCHK(get(frame + 3 * at * MR, d_frame, sizeof(double) * 3 * c * MR));
+            HIPCHK(batch_get(b, partner + at * MR, d_partner, sizeof(int32_t) * c * MR));
+            HIPCHK(batch_get(b, kind + at * MR, d_kind, sizeof(int32_t) * c * MR));
+            HIPCHK(batch_get(b, dist + at * MR, d_dist, sizeof(double) * c * MR));
+            if (pos) HIPCHK(batch_get(b, pos + 3 * at * MR, d_pos, sizeof(double) * 3 * c * MR));
+            if (frame) HIPCHK(batch_get(b, frame + 3 * at * MR, d_frame, sizeof(double) * 3 * c * MR));
         }
-        HIPCHK(hipStreamSynchronize(b->stream));     // (the next range reuses the staging buffer)
-    }
-    if (n_truncated) {
-        int64_t t = 0;
-        for (size_t k = 0; k < (size_t)n * M; ++k) t += counts[k] > R;
-        *n_truncated = t;
-    }
+        return (int)RB_OK;
+    }));
+    if (n_truncated) *n_truncated = batch_truncated(counts, (size_t)n * M, R);
     return RB_OK;
 }
 
@@ -1048,10 +1114,7 @@ int rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, int
     WCHK(batch_check_io(io_dtype));
     WCHK(batch_check_contact_law(b));
     HIPCHK(hipSetDevice(b->device));
-    const std::pair<const void *, const char *> arrays[] = {{counts, "counts"}, {partner, "partner"}, {kind, "kind"},
-                                                            {dist, "dist"},     {pos, "pos"},         {frame, "frame"}};
-    for (const auto &a : arrays)
-        if (a.first) WCHK(batch_dev_ptr(b, a.first, a.second));
+    WCHK(batch_dev_ptrs(b, {{counts, "counts"}, {partner, "partner"}, {kind, "kind"}, {dist, "dist"}, {pos, "pos"}, {frame, "frame"}}));
     ContactQuery q{};
     q.counts = counts;
     q.partner = partner;
@@ -1064,6 +1127,82 @@ int rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, int
     q.io32 = io_dtype == RB_F32;
     q.box = b->box;
     return batch_launch_contacts(b, q);
+}
+
+// ---- the impulse query ----------------------------------------------------------
+
+int rb_batch_impulses(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t max_records, double dt, double restitution,
+                      double friction, double contact_threshold, int32_t *counts, int32_t *partner, int32_t *kind,
+                      double *dist, double *jn, double *jt, double *vel, double *net, int64_t *n_truncated) {
+    ApiScope api_scope_(b ? b->device : -1);
+    const int32_t R = max_records;
+    WCHK(batch_check_impulses(b, R, counts, partner, kind, dist, jn, jt, dt, restitution, friction, contact_threshold));
+    WCHK(batch_check_query_ids(b, env_ids, n));
+    WCHK(batch_check_contact_law(b));
+    if (n_truncated) *n_truncated = 0;
+    if (n == 0) return RB_OK;
+    // one listed environment in the staging buffer: the reals first (aligned), then the words
+    const size_t M = (size_t)b->M, MR = M * (size_t)R;
+    const size_t per = sizeof(double) * (5 * MR + (vel ? 6 * M : 0) + (net ? 6 * M : 0)) + sizeof(int32_t) * (M + 2 * MR);
+    WCHK(batch_check_query_fit(b, per, "the impulse records"));
+    WCHK(batch_query_ranges(b, env_ids, n, per, [&](int64_t first, size_t c) {
+        const size_t at = (size_t)first;
+        double *d_dist = reinterpret_cast<double *>(b->con);
+        double *d_jn = d_dist + c * MR, *d_jt = d_jn + c * MR, *d_vel = d_jt + 3 * c * MR;
+        double *d_net = d_vel + (vel ? 6 * c * M : 0);
+        int32_t *d_counts = reinterpret_cast<int32_t *>(d_net + (net ? 6 * c * M : 0));
+        int32_t *d_partner = d_counts + c * M, *d_kind = d_partner + c * MR;
+        ImpulseQuery q{};
+        q.c.counts = d_counts;
+        if (R > 0) { q.c.partner = d_partner; q.c.kind = d_kind; q.c.dist = d_dist; q.jn = d_jn; q.jt = d_jt; }
+        q.vel = vel ? d_vel : nullptr;
+        q.net = net ? d_net : nullptr;
+        q.c.ids = env_ids ? b->ids + first : nullptr;
+        q.c.env0 = first;
+        q.c.n = (int64_t)c;
+        q.c.R = R;
+        q.c.io32 = 0;
+        WCHK(batch_launch_impulses(b, q, dt, restitution, friction, contact_threshold));
+        HIPCHK(batch_get(b, counts + at * M, d_counts, sizeof(int32_t) * c * M));
+        if (R > 0) {
+            HIPCHK(batch_get(b, partner + at * MR, d_partner, sizeof(int32_t) * c * MR));
+            HIPCHK(batch_get(b, kind + at * MR, d_kind, sizeof(int32_t) * c * MR));
+            HIPCHK(batch_get(b, dist + at * MR, d_dist, sizeof(double) * c * MR));
+            HIPCHK(batch_get(b, jn + at * MR, d_jn, sizeof(double) * c * MR));
+            HIPCHK(batch_get(b, jt + 3 * at * MR, d_jt, sizeof(double) * 3 * c * MR));
+        }
+        if (vel) HIPCHK(batch_get(b, vel + 6 * at * M, d_vel, sizeof(double) * 6 * c * M));
+        if (net) HIPCHK(batch_get(b, net + 6 * at * M, d_net, sizeof(double) * 6 * c * M));
+        return (int)RB_OK;
+    }));
+    if (n_truncated) *n_truncated = batch_truncated(counts, (size_t)n * M, R);
+    return RB_OK;
+}
+
+int rb_batch_impulses_dev(rb_batch *b, int32_t max_records, double dt, double restitution, double friction,
+                          double contact_threshold, int32_t *counts, int32_t *partner, int32_t *kind, void *dist, void *jn,
+                          void *jt, void *vel, void *net, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    WCHK(batch_check_impulses(b, max_records, counts, partner, kind, dist, jn, jt, dt, restitution, friction,
+                              contact_threshold));
+    WCHK(batch_check_io(io_dtype));
+    WCHK(batch_check_contact_law(b));
+    HIPCHK(hipSetDevice(b->device));
+    WCHK(batch_dev_ptrs(b, {{counts, "counts"}, {partner, "partner"}, {kind, "kind"}, {dist, "dist"}, {jn, "jn"}, {jt, "jt"},
+                            {vel, "vel"}, {net, "net"}}));
+    ImpulseQuery q{};
+    q.c.counts = counts;
+    q.c.partner = partner;
+    q.c.kind = kind;
+    q.c.dist = dist;
+    q.jn = jn;
+    q.jt = jt;
+    q.vel = vel;
+    q.net = net;
+    q.c.n = b->E;
+    q.c.R = max_records;
+    q.c.io32 = io_dtype == RB_F32;
+    return batch_launch_impulses(b, q, dt, restitution, friction, contact_threshold);
 }
 
 }  // extern "C"

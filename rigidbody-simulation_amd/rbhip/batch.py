@@ -20,6 +20,10 @@ The environments need not hold the same scene shape: a population
 count (1..M) and its own kinds.  Bodies past an environment's count are
 absent: their rows are storage that no step reads or writes, sampled runs
 hold zeros there and the contact query gives them count 0.
+contacts() lists every body's contacts of the current state; impulses() is the
+contact-force sensor: what the next step does to every body, contact by
+contact (jn and jt of collision.py:7-48, the velocity the solve leaves, the
+net contact impulse), without stepping.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
 multi_sphere_logger.py), one per environment, sampled on the device.
@@ -31,7 +35,8 @@ the batch's stream (use_stream) and return without waiting; sync() waits.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from dataclasses import dataclass
+from typing import Any, Optional
 
 import numpy as np
 
@@ -76,6 +81,33 @@ class BatchContacts:
         def pick(a):
             return None if a is None else np.asarray(a[i])[keep]
         return cnt.copy(), pick(self.partner), pick(self.kind), pick(self.dist), pick(self.pos), pick(self.frame)
+
+
+@dataclass
+class BatchImpulses:
+    """What the next step does to every body, contact by contact
+    (BatchWorld.impulses / impulses_device): dense arrays, R slots per body
+    (partner.shape[-1]; 0 and None records for the "sensor only" call).
+
+    counts (n, M), partner, kind, dist (n, M, R): word for word the fields of
+    BatchContacts for the same state and R.  jn (n, M, R), jt (n, M, R, 3):
+    the two return values of compute_collision_impulse_friction
+    (collision.py:7-48) for the contact, 0 where the step skips it or it
+    separates.  vel (n, M, 6): (v, omega) after gravity, applied forces and all
+    the body's contacts, the step's qvel.  net (n, M, 6): the body's net contact
+    impulse and net angular impulse about its centre; net[..., :3] / dt is the
+    average contact force of the step.  vel and net do not depend on R.  A
+    failed environment: counts -1, zeros elsewhere; an absent body: 0 and zeros.
+    truncated: the bodies with count > R (None for the device form)."""
+    counts: Any
+    partner: Any
+    kind: Any
+    dist: Any
+    jn: Any
+    jt: Any
+    vel: Any
+    net: Any
+    truncated: Optional[int]
 
 
 class BatchWorld:
@@ -561,3 +593,83 @@ class BatchWorld:
         if R == 0:
             return BatchContacts(0, given["counts"], None, None, None, None, None, None)
         return BatchContacts(R, *(given[k] for k in names), None)
+
+    # ---- the impulses of the next step ------------------------------------------
+    def impulses(self, envs=None, max_records=None, dt=None, restitution=None, friction=None,
+                 threshold=None) -> BatchImpulses:
+        """What the next step(1, dt, restitution, friction, threshold) does to
+        every body of the environments in envs (None: all), contact by contact:
+        the contact list of contacts(), jn and jt of every record
+        (collision.py:7-48, :72-88), the velocity the solve leaves and the
+        body's net contact impulse.  It steps nothing and changes nothing.
+        max_records as for contacts() (0: counts, vel and net only); the step
+        parameters default to the scene's, as for step().  Not under "balls"."""
+        ids, n = self._envs(envs)
+        p = self._params(dt, restitution, friction, threshold)
+        R, M = self._max_records(max_records), self.n_bodies
+        rec = R > 0
+        counts = np.zeros((n, M), np.int32)
+        partner = np.zeros((n, M, R), np.int32) if rec else None
+        kind = np.zeros((n, M, R), np.int32) if rec else None
+        dist = np.zeros((n, M, R)) if rec else None
+        jn = np.zeros((n, M, R)) if rec else None
+        jt = np.zeros((n, M, R, 3)) if rec else None
+        vel, net = np.zeros((n, M, 6)), np.zeros((n, M, 6))
+        nt = C.c_int64()
+        _lib.check(self._L.rb_batch_impulses(self._h, _lib.ptr(ids), n, R, *p, _lib.ptr(counts), _lib.ptr(partner),
+                                             _lib.ptr(kind), _lib.ptr(dist), _lib.ptr(jn), _lib.ptr(jt), _lib.ptr(vel),
+                                             _lib.ptr(net), C.byref(nt)), "rb_batch_impulses")
+        return BatchImpulses(counts, partner, kind, dist, jn, jt, vel, net, nt.value)
+
+    def impulses_device(self, max_records=None, dtype=None, out=None, dt=None, restitution=None, friction=None,
+                        threshold=None) -> BatchImpulses:
+        """impulses() of all environments into device memory, enqueued on the
+        batch's stream without waiting, with the conventions of
+        contacts_device(): a BatchImpulses whose fields are the arrays of `out`
+        (a BatchImpulses of an earlier call, or a mapping with the fields'
+        names; its max_records holds; vel and net may be left out) or new
+        torch tensors: counts, partner and kind int32, the rest of `dtype`
+        ("f64" / "f32"; None: the arrays', else the batch's).  truncated is
+        None: nothing is read back."""
+        E, M = self.n_envs, self.n_bodies
+        p = self._params(dt, restitution, friction, threshold)
+        names = ("counts", "partner", "kind", "dist", "jn", "jt", "vel", "net")
+        records = ("partner", "kind", "dist", "jn", "jt")
+        if out is not None:
+            given = {k: (out.get(k) if hasattr(out, "get") else getattr(out, k, None)) for k in names}
+            if given["counts"] is None:
+                raise ValueError("out: counts is required")
+            if given["partner"] is None:
+                R = 0
+            else:
+                try:
+                    R = int(given["partner"].__cuda_array_interface__["shape"][-1])
+                except Exception as exc:
+                    raise TypeError("partner: expected device memory (an object with __cuda_array_interface__), "
+                                    f"got {type(given['partner']).__name__}") from exc
+            if max_records is not None and int(max_records) != R:
+                raise ValueError(f"partner: {R} slots per body, max_records is {int(max_records)}")
+        else:
+            given = dict.fromkeys(names)
+            R = self._max_records(max_records)
+        if R < 0:
+            raise ValueError("max_records < 0")
+        reals = ("dist", "jn", "jt", "vel", "net")
+        ts = self._pair_typestr(reals, tuple(given[k] for k in reals), dtype)
+        if out is None:
+            given["counts"] = self._new((E, M), "<i4")
+            if R > 0:
+                given["partner"], given["kind"] = self._new((E, M, R), "<i4"), self._new((E, M, R), "<i4")
+                given["dist"], given["jn"] = self._new((E, M, R), ts), self._new((E, M, R), ts)
+                given["jt"] = self._new((E, M, R, 3), ts)
+            given["vel"], given["net"] = self._new((E, M, 6), ts), self._new((E, M, 6), ts)
+        shapes = {"counts": ((E, M), ("<i4",)), "partner": ((E, M, R), ("<i4",)), "kind": ((E, M, R), ("<i4",)),
+                  "dist": ((E, M, R), (ts,)), "jn": ((E, M, R), (ts,)), "jt": ((E, M, R, 3), (ts,)),
+                  "vel": ((E, M, 6), (ts,)), "net": ((E, M, 6), (ts,))}
+        ptrs = {k: None if given[k] is None else _device_array(k, given[k], *shapes[k], out=True)[0] for k in names}
+        have = [ptrs[k] is not None for k in records]
+        if (R > 0 and not all(have)) or (R == 0 and any(have)):
+            raise ValueError("partner, kind, dist, jn and jt: all five with max_records > 0, none with 0")
+        _lib.check(self._L.rb_batch_impulses_dev(self._h, R, *p, *(ptrs[k] for k in names), _IO_CODES[ts]),
+                   "rb_batch_impulses_dev")
+        return BatchImpulses(*(given[k] for k in names), None)

@@ -63,6 +63,14 @@ of the same batch, and the host form contacts(R) against get_state(),
 alternating; seconds per call.  With --box-pile NX,NY,LAYERS the scene is that
 pile (the mixed-template instance of the query's kernel).
 
+--impulses R: instead, the impulse query with R records per body (0: the
+"sensor only" call) on a batch that has stepped `--steps` steps:
+impulses_device(R) per call (tensors allocated once, 20 calls and one sync()
+per window) against one step_async(1) and against contacts_device(R, without
+geometry) of the same batch, alternating; seconds per call.  With --box-pile
+NX,NY,LAYERS the scene is that pile (the box instances of the query's
+kernel).  Writes to profiles/batch_impulses/ unless --out is given.
+
 --ragged LO,HI: instead, an ensemble of E scenes whose body counts are spread
 evenly over LO..HI (--ragged-scene flat_spheres: rows of spheres; box_pile:
 columns of two cubes, the first n bodies), f64.  Three measurements in one
@@ -391,6 +399,48 @@ def bench_contacts(rb, sc, E, R, settle, reps, dtype, calls=20):
     return res
 
 
+def bench_impulses(rb, sc, E, R, settle, reps, dtype, calls=20):
+    """Seconds per call of the impulse query on a batch that has stepped
+    `settle` steps: impulses_device(R) into tensors allocated once against one
+    step_async(1) and against contacts_device(R) without geometry (each `calls`
+    calls and one sync() per window), alternating; the host form once, for the
+    comparison of the two forms."""
+    import torch
+    with rb.BatchWorld(sc, E, dtype=dtype) as b:
+        b.set_params(restitution=np.linspace(0.5, 1.0, E))
+        b.use_stream(torch.cuda.current_stream().cuda_stream)
+        if b.step(settle):
+            raise RuntimeError("environments failed")
+        out = b.impulses_device(max_records=R)
+        con = b.contacts_device(max_records=R, geometry=False)
+        b.sync()
+        host = b.impulses(max_records=R)                # warm-up, and the comparison
+        fields = ("counts", "vel", "net") + (("partner", "kind", "dist", "jn", "jt") if R > 0 else ())
+        same = bool(all(np.array_equal(getattr(out, f).cpu().numpy(), getattr(host, f)) for f in fields))
+        listed = int(np.maximum(host.counts, 0).sum())
+        applied = int((host.jn != 0).sum()) if R > 0 else None
+        q0, v0 = b.get_state()
+        t = {"impulses_device": [], "contacts_device": [], "step_async_1": []}
+
+        def window(name, f, n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                f()
+            b.sync()
+            t[name].append((time.perf_counter() - t0) / n)
+
+        for _ in range(reps):
+            window("impulses_device", lambda: b.impulses_device(out=out), calls)
+            window("contacts_device", lambda: b.contacts_device(out=con), calls)
+            window("step_async_1", lambda: b.step_async(1), calls)
+            b.set_state(q0, v0)
+    res = dict(max_records=R, settle_steps=settle, calls_per_window=calls, contacts_listed=listed, nonzero_jn=applied,
+               truncated=host.truncated, identical=same, **{k: _summary(v) for k, v in t.items()})
+    res["impulses_over_step"] = res["impulses_device"]["median"] / res["step_async_1"]["median"]
+    res["impulses_over_contacts"] = res["impulses_device"]["median"] / res["contacts_device"]["median"]
+    return res
+
+
 def ragged_scene(variant, n, seed):
     """A scene of n bodies: a row of spheres, or the first n bodies of columns of two cubes."""
     from rbhip import scenes
@@ -495,6 +545,8 @@ def main():
                     help="time run_sampled_device(steps, EVERY) against run_sampled(steps, EVERY)")
     ap.add_argument("--contacts", type=int, default=-1, metavar="R",
                     help="time the contact query with R records per body, after --steps settling steps")
+    ap.add_argument("--impulses", type=int, default=-1, metavar="R",
+                    help="time the impulse query with R records per body, after --steps settling steps")
     ap.add_argument("--ragged", default="", metavar="LO,HI",
                     help="an ensemble with body counts spread over LO..HI: one ragged batch against one batch per shape")
     ap.add_argument("--ragged-scene", default="flat_spheres", choices=["flat_spheres", "box_pile"])
@@ -503,6 +555,9 @@ def main():
     if not a.out:
         a.out = os.path.join(ROOT, "profiles", "batch_ragged", f"ragged_{a.ragged_scene}_{a.ragged.replace(',', '_')}.json") \
             if a.ragged else os.path.join(ROOT, "profiles", "batch", "batch_bench.json")
+        if a.impulses >= 0:
+            scene = "box_pile_" + a.box_pile.replace(",", "_") if a.box_pile else "multi_sphere4"
+            a.out = os.path.join(ROOT, "profiles", "batch_impulses", f"impulses_{scene}_R{a.impulses}.json")
 
     import rbhip
     from rbhip import scenes
@@ -515,13 +570,22 @@ def main():
         res["law"] = a.law
     if a.ragged:
         if a.law != "mujoco" or a.dtype != "f64" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or \
-                a.sampled_device or a.contacts >= 0 or a.box_pile or a.wide_pile:
+                a.sampled_device or a.contacts >= 0 or a.impulses >= 0 or a.box_pile or a.wide_pile:
             raise SystemExit("--ragged: on its own, f64, under the default law")
         lo, hi = (int(t) for t in a.ragged.split(","))
         if not 1 <= lo <= hi <= 256:
             raise SystemExit("--ragged LO,HI: 1 <= LO <= HI <= 256")
         res.update(scene=f"ragged {a.ragged_scene}", bodies_per_env=hi, counts=f"{lo}..{hi}")
         res["ragged"] = {str(E): bench_ragged(rbhip, a.ragged_scene, lo, hi, E, a.steps, a.reps) for E in a.envs}
+    elif a.impulses >= 0:
+        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or a.sampled_device or \
+                a.contacts >= 0 or a.wide_pile:
+            raise SystemExit("--impulses: on its own (with --box-pile for a mixed template), under the default law")
+        if a.box_pile:
+            sc = scenes.box_pile(*(int(t) for t in a.box_pile.split(",")))
+            res.update(scene=sc.name, bodies_per_env=sc.n)
+        res.update(unit="seconds per call")
+        res["impulses"] = {str(E): bench_impulses(rbhip, sc, E, a.impulses, a.steps, a.reps, a.dtype) for E in a.envs}
     elif a.contacts >= 0:
         if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or a.sampled_device:
             raise SystemExit("--contacts: on its own (with --box-pile for a mixed template), under the default law")
