@@ -1,5 +1,6 @@
 // rb_api_common.hip — what every unit of the implementation of include/rbhip.h
-// shares at run time: the thread gate's state, the error text.
+// shares at run time: the thread gate's state, the error text, the grow-only
+// device buffer and the device-memory pointer check of worlds and batches.
 //
 // A world owns its device buffers — struct-of-arrays state, replicated
 // constants, two ping-pong position snapshots (which double as the
@@ -111,6 +112,29 @@ int err_to_code(int32_t bits) {
         return fail(RB_EUNSUPPORTED, "device: box-involved pair within contact range with no box kernel to take it");
     if (bits & ERR_PARTNER_OVERFLOW) return fail(RB_EOVERFLOW, "device: a body has more sphere partners than max_partners");
     if (bits & ERR_BUCKET_OVERFLOW) return fail(RB_EOVERFLOW, "device: more than 30 bodies hashed to one broadphase bucket");
+    return RB_OK;
+}
+
+int grow(void **buf, size_t *cap, size_t need) {
+    if (need <= *cap) return RB_OK;
+    if (*buf) { HIPCHK(hipFree(*buf)); *buf = nullptr; }
+    *cap = 0;
+    HIPCHK(hipMalloc(buf, need));
+    *cap = need;
+    return RB_OK;
+}
+
+int dev_ptrs(int device, const char *owner, std::initializer_list<std::pair<const void *, const char *>> arrays) {
+    for (const auto &[p, name] : arrays) {
+        if (!p) continue;
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            return fail(RB_EINVAL, "%s is not device memory (a host pointer?)", name);
+        }
+        if (a.device != device)
+            return fail(RB_EINVAL, "%s is memory of device %d, the %s is on device %d", name, a.device, owner, device);
+    }
     return RB_OK;
 }
 

@@ -12,6 +12,7 @@
 // the world that a step, a graph, the stats or the boundary reads: the fields
 // written are the cq_* ones alone.
 #include "rb_host.hpp"
+#include "rb_stagelayout.hpp"
 #include "rb_world_contacts.hpp"
 
 namespace rb::host {
@@ -132,31 +133,18 @@ static int query_launch(rb_world *w, int64_t first, int64_t count, int32_t R, in
     return RB_OK;
 }
 
-static int query_dev_ptr(const rb_world *w, const void *p, const char *name) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(RB_EINVAL, "%s is not device memory (a host pointer?)", name);
-    }
-    if (a.device != w->device) return fail(RB_EINVAL, "%s is memory of device %d, the world is on device %d", name, a.device, w->device);
-    return RB_OK;
-}
-
 // The staging of the host form: a device buffer and its pinned twin, grown
-// on demand up to the world's bound.  Per body: the reals first (so every
-// array of a sub-range starts aligned), then the words.
-static size_t stage_per_body(int32_t R, bool pos, bool frame) {
-    return sizeof(double) * (size_t)R * (1 + (pos ? 3 : 0) + (frame ? 3 : 0)) + sizeof(int32_t) * (1 + 2 * (size_t)R);
-}
+// on demand up to the world's bound (laid out by rb_stagelayout.hpp, a body
+// per unit).  cq_stage_bytes counts once both stand.
 static int stage_reserve(rb_world *w, size_t bytes) {
     if (bytes <= w->cq_stage_bytes) return RB_OK;
     HIPCHK(hipStreamSynchronize(w->stream));
-    if (w->cq_stage) { HIPCHK(hipFree(w->cq_stage)); w->cq_stage = nullptr; }
     if (w->cq_stage_h) { HIPCHK(hipHostFree(w->cq_stage_h)); w->cq_stage_h = nullptr; }
+    size_t cap = 0;
     w->cq_stage_bytes = 0;
-    HIPCHK(hipMalloc((void **)&w->cq_stage, bytes));
+    WCHK(grow((void **)&w->cq_stage, &cap, bytes));
     HIPCHK(hipHostMalloc((void **)&w->cq_stage_h, bytes, hipHostMallocDefault));
-    w->cq_stage_bytes = bytes;
+    w->cq_stage_bytes = cap;
     return RB_OK;
 }
 
@@ -174,46 +162,35 @@ int rb_query_contacts(rb_world *w, int64_t first, int64_t count, int32_t max_rec
     WCHK(query_supported(w));
     if (n_truncated) *n_truncated = 0;
     if (count == 0) return RB_OK;
-    const size_t per = stage_per_body(R, pos, frame);
+    const StageLayout lay = stage_contacts(1, R, pos, frame);
+    const size_t per = lay.per();
     if (per > w->cq_limit)
         return fail(RB_EINVAL, "the contact list of one body (%zu bytes) does not fit the staging buffer (%zu bytes: "
                                "RBHIP_CONTACT_STAGE_BYTES)", per, w->cq_limit);
-    const int64_t fit = std::min<int64_t>(count, (int64_t)(w->cq_limit / per));
+    const int64_t fit = std::min<int64_t>(count, lay.fit(w->cq_limit));
     HIPCHK(hipSetDevice(w->device));
     if (int rc = finish_pending(w)) return rc;
     WCHK(stage_reserve(w, per * (size_t)fit));
     WCHK(query_fill(w));
     // a sub-range of the bodies per launch: one DMA per array into the pinned
     // twin, then out to the caller
+    void *const dst[SC_FIELDS] = {dist, pos, frame, counts, partner, kind};
     for (int64_t at0 = 0; at0 < count; at0 += fit) {
-        const size_t c = (size_t)std::min<int64_t>(fit, count - at0), cR = c * (size_t)R, at = (size_t)at0;
-        const size_t o_dist = 0, o_pos = o_dist + sizeof(double) * cR, o_frame = o_pos + (pos ? sizeof(double) * 3 * cR : 0);
-        const size_t o_counts = o_frame + (frame ? sizeof(double) * 3 * cR : 0), o_partner = o_counts + sizeof(int32_t) * c;
-        const size_t o_kind = o_partner + sizeof(int32_t) * cR;
+        const size_t c = (size_t)std::min<int64_t>(fit, count - at0);
         char *d = w->cq_stage, *h = w->cq_stage_h;
-        WCHK(query_launch(w, first + at0, (int64_t)c, R, (int32_t *)(d + o_counts), R > 0 ? (int32_t *)(d + o_partner) : nullptr,
-                          R > 0 ? (int32_t *)(d + o_kind) : nullptr, R > 0 ? d + o_dist : nullptr, pos ? d + o_pos : nullptr,
-                          frame ? d + o_frame : nullptr, false));
-        struct Move { void *dst; size_t off, bytes; };
-        const Move moves[] = {{counts + at, o_counts, sizeof(int32_t) * c},
-                              {partner ? partner + at * R : nullptr, o_partner, sizeof(int32_t) * cR},
-                              {kind ? kind + at * R : nullptr, o_kind, sizeof(int32_t) * cR},
-                              {dist ? dist + at * R : nullptr, o_dist, sizeof(double) * cR},
-                              {pos ? pos + 3 * at * R : nullptr, o_pos, sizeof(double) * 3 * cR},
-                              {frame ? frame + 3 * at * R : nullptr, o_frame, sizeof(double) * 3 * cR}};
-        for (const Move &m : moves)
-            if (m.dst && m.bytes) HIPCHK(hipMemcpyAsync(h + m.off, d + m.off, m.bytes, hipMemcpyDeviceToHost, w->stream));
+        WCHK(query_launch(w, first + at0, (int64_t)c, R, (int32_t *)lay.at(d, SC_COUNTS, c), (int32_t *)lay.at(d, SC_PARTNER, c),
+                          (int32_t *)lay.at(d, SC_KIND, c), lay.at(d, SC_DIST, c), lay.at(d, SC_POS, c), lay.at(d, SC_FRAME, c),
+                          false));
+        for (int f = 0; f < lay.n; ++f)
+            if (lay.unit[f])
+                HIPCHK(hipMemcpyAsync(h + lay.offset(f, c), d + lay.offset(f, c), lay.bytes(f, c), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(hipStreamSynchronize(w->stream));     // (the next sub-range reuses the staging)
-        for (const Move &m : moves)
-            if (m.dst && m.bytes) memcpy(m.dst, h + m.off, m.bytes);
+        for (int f = 0; f < lay.n; ++f)
+            if (lay.unit[f]) memcpy((char *)dst[f] + lay.caller(f, (size_t)at0), h + lay.offset(f, c), lay.bytes(f, c));
     }
-    int64_t trunc = 0, bad = -1;
-    for (int64_t k = 0; k < count; ++k) {
-        trunc += counts[k] > R;
-        if (counts[k] == QUERY_NO_LIST && bad < 0) bad = k;
-    }
-    if (n_truncated) *n_truncated = trunc;
-    if (bad >= 0) {
+    if (n_truncated) *n_truncated = count_truncated(counts, (size_t)count, R);
+    const int64_t bad = std::find(counts, counts + count, QUERY_NO_LIST) - counts;     // the first body without a list
+    if (bad < count) {
         int32_t bits = 0;
         WCHK(wget(w, &bits, w->cq_words + 1, sizeof bits));
         if (bits & ERR_BUCKET_OVERFLOW)
@@ -235,10 +212,8 @@ int rb_query_contacts_dev(rb_world *w, int64_t first, int64_t count, int32_t max
     WCHK(query_supported(w));
     if (count == 0) return RB_OK;
     HIPCHK(hipSetDevice(w->device));
-    const std::pair<const void *, const char *> arrays[] = {{counts, "counts"}, {partner, "partner"}, {kind, "kind"},
-                                                            {dist, "dist"},     {pos, "pos"},         {frame, "frame"}};
-    for (const auto &a : arrays)
-        if (a.first) WCHK(query_dev_ptr(w, a.first, a.second));
+    WCHK(dev_ptrs(w->device, "world", {{counts, "counts"}, {partner, "partner"}, {kind, "kind"}, {dist, "dist"}, {pos, "pos"},
+                                        {frame, "frame"}}));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(w->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
         return fail(RB_EUNSUPPORTED, "the contact query is not supported under a stream capture");

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <tuple>
 #include <vector>
@@ -285,6 +286,20 @@ inline int wget(rb_world *w, void *dst, const void *src, size_t bytes) {
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
     return RB_OK;
+}
+
+// A device buffer that only grows: afterwards *buf holds `need` bytes or more.
+// (The capacity is zero while the buffer is being replaced: an error in between
+// leaves an empty buffer, not a dangling one.)
+int grow(void **buf, size_t *cap, size_t need);
+// Every array of a device form that is given: device memory on `device`.
+// owner: "batch" / "world", for the message.  (A refusal leaves no HIP error behind.)
+int dev_ptrs(int device, const char *owner, std::initializer_list<std::pair<const void *, const char *>> arrays);
+// the bodies of a host-form query whose true count is past R
+inline int64_t count_truncated(const int32_t *counts, size_t bodies, int32_t R) {
+    int64_t t = 0;
+    for (size_t k = 0; k < bodies; ++k) t += counts[k] > R;
+    return t;
 }
 
 template <typename T> T *dp(void *p, int64_t off) { return reinterpret_cast<T *>(p) + off; }

@@ -41,8 +41,14 @@ from typing import Any, Optional
 import numpy as np
 
 from . import _lib
-from ._devarray import _IO_CODES, _device_array, _new_tensor, _pair_typestr
+from ._devarray import (_CONTACT_FIELDS, _IO_CODES, _device_array, _host_arrays, _new_tensor, _pair_typestr,
+                        _resolve_out)
 from .scenes import Scene
+
+
+# the arrays of the impulse query (_devarray._CONTACT_FIELDS: name, record, tail, real)
+_IMPULSE_FIELDS = _CONTACT_FIELDS[:4] + (("jn", True, (), True), ("jt", True, (3,), True),
+                                         ("vel", False, (6,), True), ("net", False, (6,), True))
 
 
 class BatchContacts:
@@ -186,15 +192,25 @@ class BatchWorld:
                                ("normal convention", sc.normal_convention == t.normal_convention)):
                 if not same:
                     raise ValueError(f"from_scenes: scene {k} ({sc.name!r}) differs from scene 0 in its {what}")
+        return cls._apply_scenes(t, scenes, kw, None, np.stack([sc.mass for sc in scenes]),
+                                 np.stack([sc.inertia for sc in scenes]), np.stack([sc.size for sc in scenes]),
+                                 np.stack([sc.qpos0 for sc in scenes]), np.stack([sc.qvel0 for sc in scenes]))
+
+    @classmethod
+    def _apply_scenes(cls, t, scenes, kw, population, mass, inertia, size, qpos, qvel):
+        """The batch of template t with an environment per scene: the
+        population (None: none), the scenes' planes, gravity and parameters,
+        the given constants and state.  Closed again if any is refused."""
         b = cls(t, len(scenes), **kw)
         try:
+            if population is not None:
+                b.set_population(*population)
             if np.shape(t.planes)[0]:
                 b.set_planes(np.stack([np.asarray(sc.planes, np.float64) for sc in scenes]))
             b.set_gravity(np.stack([np.asarray(sc.gravity, np.float64) for sc in scenes]))
             b.set_params(restitution=[sc.restitution for sc in scenes], friction=[sc.friction for sc in scenes])
-            b.set_bodies(mass=np.stack([sc.mass for sc in scenes]), inertia=np.stack([sc.inertia for sc in scenes]),
-                         size=np.stack([sc.size for sc in scenes]))
-            b.set_state(np.stack([sc.qpos0 for sc in scenes]), np.stack([sc.qvel0 for sc in scenes]))
+            b.set_bodies(mass=mass, inertia=inertia, size=size)
+            b.set_state(qpos, qvel)
         except Exception:
             b.close()
             raise
@@ -235,19 +251,7 @@ class BatchWorld:
         for e, sc in enumerate(scenes):
             kinds[e, :sc.n], mass[e, :sc.n], inertia[e, :sc.n], size[e, :sc.n] = sc.kind, sc.mass, sc.inertia, sc.size
             qpos[e, :sc.n], qvel[e, :sc.n] = sc.qpos0, sc.qvel0
-        b = cls(t, E, **kw)
-        try:
-            b.set_population(n, kinds)
-            if np.shape(t.planes)[0]:
-                b.set_planes(np.stack([np.asarray(sc.planes, np.float64) for sc in scenes]))
-            b.set_gravity(np.stack([np.asarray(sc.gravity, np.float64) for sc in scenes]))
-            b.set_params(restitution=[sc.restitution for sc in scenes], friction=[sc.friction for sc in scenes])
-            b.set_bodies(mass=mass, inertia=inertia, size=size)
-            b.set_state(qpos, qvel)
-        except Exception:
-            b.close()
-            raise
-        return b
+        return cls._apply_scenes(t, scenes, kw, (n, kinds), mass, inertia, size, qpos, qvel)
 
     # ---- lifetime ---------------------------------------------------------
     def close(self):
@@ -434,18 +438,11 @@ class BatchWorld:
         Not under "balls"."""
         ids, n = self._envs(envs)
         R, M = self._max_records(max_records), self.n_bodies
-        counts = np.zeros((n, M), np.int32)
-        rec = R > 0
-        partner = np.zeros((n, M, R), np.int32) if rec else None
-        kind = np.zeros((n, M, R), np.int32) if rec else None
-        dist = np.zeros((n, M, R)) if rec else None
-        pos = np.zeros((n, M, R, 3)) if rec and geometry else None
-        frame = np.zeros((n, M, R, 3)) if rec and geometry else None
+        a = _host_arrays(_CONTACT_FIELDS, (n, M), R, skip=() if geometry else ("pos", "frame"))
         nt = C.c_int64()
-        _lib.check(self._L.rb_batch_contacts(self._h, _lib.ptr(ids), n, R, _lib.ptr(counts), _lib.ptr(partner),
-                                             _lib.ptr(kind), _lib.ptr(dist), _lib.ptr(pos), _lib.ptr(frame),
+        _lib.check(self._L.rb_batch_contacts(self._h, _lib.ptr(ids), n, R, *(_lib.ptr(v) for v in a.values()),
                                              C.byref(nt)), "rb_batch_contacts")
-        return BatchContacts(R, counts, partner, kind, dist, pos, frame, nt.value)
+        return BatchContacts(R, *a.values(), nt.value)
 
     # ---- the device-resident boundary ---------------------------------------
     # Arrays are objects with __cuda_array_interface__ on the batch's device,
@@ -473,19 +470,13 @@ class BatchWorld:
         _lib.check(self._L.rb_batch_sync(self._h, C.byref(nf)), "rb_batch_sync")
         return nf.value
 
-    def _pair_typestr(self, names, arrays, dtype):
-        return _pair_typestr(self.dtype, names, arrays, dtype)
-
-    def _new(self, shape, typestr):
-        return _new_tensor(shape, typestr, self.device)
-
     def set_state_device(self, qpos, qvel, mask=None):
         """set_state() from device arrays qpos (E, M, 7), qvel (E, M, 6) of one
         element type.  mask (E,) bool or uint8 on the device: only the
         environments where it is set are written and reset (None: all); the
         rows of the others are not read."""
         E, M = self.n_envs, self.n_bodies
-        ts = self._pair_typestr(("qpos", "qvel"), (qpos, qvel), None)
+        ts = _pair_typestr(self.dtype, ("qpos", "qvel"), (qpos, qvel), None)
         q, _ = _device_array("qpos", qpos, (E, M, 7), (ts,))
         v, _ = _device_array("qvel", qvel, (E, M, 6), (ts,))
         m = None if mask is None else _device_array("mask", mask, (E,), ("|b1", "|u1"))[0]
@@ -496,9 +487,9 @@ class BatchWorld:
         out_qpos / out_qvel, or into new torch tensors of `dtype` ("f64" /
         "f32"; None: the batch's), valid on the batch's stream."""
         E, M = self.n_envs, self.n_bodies
-        ts = self._pair_typestr(("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
-        q = self._new((E, M, 7), ts) if out_qpos is None else out_qpos
-        v = self._new((E, M, 6), ts) if out_qvel is None else out_qvel
+        ts = _pair_typestr(self.dtype, ("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
+        q = _new_tensor((E, M, 7), ts, self.device) if out_qpos is None else out_qpos
+        v = _new_tensor((E, M, 6), ts, self.device) if out_qvel is None else out_qvel
         qp, _ = _device_array("out_qpos", q, (E, M, 7), (ts,), out=True)
         vp, _ = _device_array("out_qvel", v, (E, M, 6), (ts,), out=True)
         _lib.check(self._L.rb_batch_get_state_dev(self._h, qp, vp, _IO_CODES[ts]), "rb_batch_get_state_dev")
@@ -509,15 +500,15 @@ class BatchWorld:
         found on the device: the upload then writes nothing and the next
         sync() raises; the batch counts as having forces set either way
         (set_xfrc(None) clears them).  Not under "balls"."""
-        ts = self._pair_typestr(("xfrc",), (xfrc,), None)
+        ts = _pair_typestr(self.dtype, ("xfrc",), (xfrc,), None)
         x, _ = _device_array("xfrc", xfrc, (self.n_envs, self.n_bodies, 6), (ts,))
         _lib.check(self._L.rb_batch_set_xfrc_dev(self._h, x, _IO_CODES[ts]), "rb_batch_set_xfrc_dev")
 
     def status_device(self, out_code=None, out_steps=None):
         """status() into device arrays: (code (E,) int32, steps_done (E,) int64)."""
         E = self.n_envs
-        code = self._new((E,), "<i4") if out_code is None else out_code
-        done = self._new((E,), "<i8") if out_steps is None else out_steps
+        code = _new_tensor((E,), "<i4", self.device) if out_code is None else out_code
+        done = _new_tensor((E,), "<i8", self.device) if out_steps is None else out_steps
         cp, _ = _device_array("out_code", code, (E,), ("<i4",), out=True)
         dp, _ = _device_array("out_steps", done, (E,), ("<i8",), out=True)
         _lib.check(self._L.rb_batch_status_dev(self._h, cp, dp), "rb_batch_status_dev")
@@ -535,9 +526,9 @@ class BatchWorld:
         E, M = self.n_envs, self.n_bodies
         if not velocities and out_qvel is not None:
             raise ValueError("out_qvel: given with velocities=False")
-        ts = self._pair_typestr(("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
-        q = self._new((S, E, M, 7), ts) if out_qpos is None else out_qpos
-        v = None if not velocities else self._new((S, E, M, 6), ts) if out_qvel is None else out_qvel
+        ts = _pair_typestr(self.dtype, ("out_qpos", "out_qvel"), (out_qpos, out_qvel), dtype)
+        q = _new_tensor((S, E, M, 7), ts, self.device) if out_qpos is None else out_qpos
+        v = None if not velocities else _new_tensor((S, E, M, 6), ts, self.device) if out_qvel is None else out_qvel
         qp, _ = _device_array("out_qpos", q, (S, E, M, 7), (ts,), out=True)
         vp = None if v is None else _device_array("out_qvel", v, (S, E, M, 6), (ts,), out=True)[0]
         if S > 0 and v is not None and vp is None:
@@ -554,45 +545,12 @@ class BatchWorld:
         torch tensors: counts, partner and kind int32, dist, pos and frame of
         `dtype` ("f64" / "f32"; None: the arrays', else the batch's).
         truncated is None: nothing is read back."""
-        E, M = self.n_envs, self.n_bodies
-        names = ("counts", "partner", "kind", "dist", "pos", "frame")
-        if out is not None:
-            given = {k: (out.get(k) if hasattr(out, "get") else getattr(out, k, None)) for k in names}
-            if given["counts"] is None:
-                raise ValueError("out: counts is required")
-            if given["partner"] is None:
-                R = 0
-            else:
-                try:
-                    R = int(given["partner"].__cuda_array_interface__["shape"][-1])
-                except Exception as exc:
-                    raise TypeError("partner: expected device memory (an object with __cuda_array_interface__), "
-                                    f"got {type(given['partner']).__name__}") from exc
-            if max_records is not None and int(max_records) != R:
-                raise ValueError(f"partner: {R} slots per body, max_records is {int(max_records)}")
-        else:
-            given = dict.fromkeys(names)
-            R = self._max_records(max_records)
-        if R < 0:
-            raise ValueError("max_records < 0")
-        ts = self._pair_typestr(("dist", "pos", "frame"), (given["dist"], given["pos"], given["frame"]), dtype)
-        if out is None:
-            given["counts"] = self._new((E, M), "<i4")
-            if R > 0:
-                given["partner"], given["kind"] = self._new((E, M, R), "<i4"), self._new((E, M, R), "<i4")
-                given["dist"] = self._new((E, M, R), ts)
-                if geometry:
-                    given["pos"], given["frame"] = self._new((E, M, R, 3), ts), self._new((E, M, R, 3), ts)
-        shapes = {"counts": ((E, M), ("<i4",)), "partner": ((E, M, R), ("<i4",)), "kind": ((E, M, R), ("<i4",)),
-                  "dist": ((E, M, R), (ts,)), "pos": ((E, M, R, 3), (ts,)), "frame": ((E, M, R, 3), (ts,))}
-        ptrs = {k: None if given[k] is None else _device_array(k, given[k], *shapes[k], out=True)[0] for k in names}
-        if R > 0 and None in (ptrs["partner"], ptrs["kind"], ptrs["dist"]):
-            raise ValueError("partner, kind and dist: all three are required with max_records > 0")
-        _lib.check(self._L.rb_batch_contacts_dev(self._h, R, *(ptrs[k] for k in names), _IO_CODES[ts]),
-                   "rb_batch_contacts_dev")
-        if R == 0:
-            return BatchContacts(0, given["counts"], None, None, None, None, None, None)
-        return BatchContacts(R, *(given[k] for k in names), None)
+        R, ts, given, ptrs = _resolve_out(
+            _CONTACT_FIELDS, (self.n_envs, self.n_bodies), ("partner", "kind", "dist"),
+            "partner, kind and dist: all three are required with max_records > 0", out, max_records, dtype,
+            self.dtype, self.device, lambda: self._max_records(max_records), skip=() if geometry else ("pos", "frame"))
+        _lib.check(self._L.rb_batch_contacts_dev(self._h, R, *ptrs.values(), _IO_CODES[ts]), "rb_batch_contacts_dev")
+        return BatchContacts(R, *given.values(), None)      # (with R == 0 the library takes counts alone)
 
     # ---- the impulses of the next step ------------------------------------------
     def impulses(self, envs=None, max_records=None, dt=None, restitution=None, friction=None,
@@ -607,19 +565,11 @@ class BatchWorld:
         ids, n = self._envs(envs)
         p = self._params(dt, restitution, friction, threshold)
         R, M = self._max_records(max_records), self.n_bodies
-        rec = R > 0
-        counts = np.zeros((n, M), np.int32)
-        partner = np.zeros((n, M, R), np.int32) if rec else None
-        kind = np.zeros((n, M, R), np.int32) if rec else None
-        dist = np.zeros((n, M, R)) if rec else None
-        jn = np.zeros((n, M, R)) if rec else None
-        jt = np.zeros((n, M, R, 3)) if rec else None
-        vel, net = np.zeros((n, M, 6)), np.zeros((n, M, 6))
+        a = _host_arrays(_IMPULSE_FIELDS, (n, M), R)
         nt = C.c_int64()
-        _lib.check(self._L.rb_batch_impulses(self._h, _lib.ptr(ids), n, R, *p, _lib.ptr(counts), _lib.ptr(partner),
-                                             _lib.ptr(kind), _lib.ptr(dist), _lib.ptr(jn), _lib.ptr(jt), _lib.ptr(vel),
-                                             _lib.ptr(net), C.byref(nt)), "rb_batch_impulses")
-        return BatchImpulses(counts, partner, kind, dist, jn, jt, vel, net, nt.value)
+        _lib.check(self._L.rb_batch_impulses(self._h, _lib.ptr(ids), n, R, *p, *(_lib.ptr(v) for v in a.values()),
+                                             C.byref(nt)), "rb_batch_impulses")
+        return BatchImpulses(*a.values(), nt.value)
 
     def impulses_device(self, max_records=None, dtype=None, out=None, dt=None, restitution=None, friction=None,
                         threshold=None) -> BatchImpulses:
@@ -631,45 +581,10 @@ class BatchWorld:
         torch tensors: counts, partner and kind int32, the rest of `dtype`
         ("f64" / "f32"; None: the arrays', else the batch's).  truncated is
         None: nothing is read back."""
-        E, M = self.n_envs, self.n_bodies
         p = self._params(dt, restitution, friction, threshold)
-        names = ("counts", "partner", "kind", "dist", "jn", "jt", "vel", "net")
-        records = ("partner", "kind", "dist", "jn", "jt")
-        if out is not None:
-            given = {k: (out.get(k) if hasattr(out, "get") else getattr(out, k, None)) for k in names}
-            if given["counts"] is None:
-                raise ValueError("out: counts is required")
-            if given["partner"] is None:
-                R = 0
-            else:
-                try:
-                    R = int(given["partner"].__cuda_array_interface__["shape"][-1])
-                except Exception as exc:
-                    raise TypeError("partner: expected device memory (an object with __cuda_array_interface__), "
-                                    f"got {type(given['partner']).__name__}") from exc
-            if max_records is not None and int(max_records) != R:
-                raise ValueError(f"partner: {R} slots per body, max_records is {int(max_records)}")
-        else:
-            given = dict.fromkeys(names)
-            R = self._max_records(max_records)
-        if R < 0:
-            raise ValueError("max_records < 0")
-        reals = ("dist", "jn", "jt", "vel", "net")
-        ts = self._pair_typestr(reals, tuple(given[k] for k in reals), dtype)
-        if out is None:
-            given["counts"] = self._new((E, M), "<i4")
-            if R > 0:
-                given["partner"], given["kind"] = self._new((E, M, R), "<i4"), self._new((E, M, R), "<i4")
-                given["dist"], given["jn"] = self._new((E, M, R), ts), self._new((E, M, R), ts)
-                given["jt"] = self._new((E, M, R, 3), ts)
-            given["vel"], given["net"] = self._new((E, M, 6), ts), self._new((E, M, 6), ts)
-        shapes = {"counts": ((E, M), ("<i4",)), "partner": ((E, M, R), ("<i4",)), "kind": ((E, M, R), ("<i4",)),
-                  "dist": ((E, M, R), (ts,)), "jn": ((E, M, R), (ts,)), "jt": ((E, M, R, 3), (ts,)),
-                  "vel": ((E, M, 6), (ts,)), "net": ((E, M, 6), (ts,))}
-        ptrs = {k: None if given[k] is None else _device_array(k, given[k], *shapes[k], out=True)[0] for k in names}
-        have = [ptrs[k] is not None for k in records]
-        if (R > 0 and not all(have)) or (R == 0 and any(have)):
-            raise ValueError("partner, kind, dist, jn and jt: all five with max_records > 0, none with 0")
-        _lib.check(self._L.rb_batch_impulses_dev(self._h, R, *p, *(ptrs[k] for k in names), _IO_CODES[ts]),
-                   "rb_batch_impulses_dev")
-        return BatchImpulses(*(given[k] for k in names), None)
+        R, ts, given, ptrs = _resolve_out(
+            _IMPULSE_FIELDS, (self.n_envs, self.n_bodies), ("partner", "kind", "dist", "jn", "jt"),
+            "partner, kind, dist, jn and jt: all five with max_records > 0, none with 0", out, max_records, dtype,
+            self.dtype, self.device, lambda: self._max_records(max_records), exclusive=True)
+        _lib.check(self._L.rb_batch_impulses_dev(self._h, R, *p, *ptrs.values(), _IO_CODES[ts]), "rb_batch_impulses_dev")
+        return BatchImpulses(*given.values(), None)

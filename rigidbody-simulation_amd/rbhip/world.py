@@ -14,7 +14,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._devarray import _IO_CODES, _device_array, _new_tensor, _pair_typestr
+from ._devarray import (_CONTACT_FIELDS, _IO_CODES, _device_array, _host_arrays, _new_tensor, _pair_typestr,
+                        _resolve_out)
 from .scenes import Scene
 
 COMM_ID_BYTES = 128      # ncclUniqueId (rccl.h NCCL_UNIQUE_ID_BYTES)
@@ -358,20 +359,13 @@ class World:
         "balls"."""
         first, count, R = self._query_range(first, count, max_records, geometry)
         c = max(count, 0)
-        counts = np.zeros((1, c), np.int32)
-        rec = R > 0
-        partner = np.zeros((1, c, R), np.int32) if rec else None
-        kind = np.zeros((1, c, R), np.int32) if rec else None
-        dist = np.zeros((1, c, R)) if rec else None
-        pos = np.zeros((1, c, R, 3)) if rec and geometry else None
-        frame = np.zeros((1, c, R, 3)) if rec and geometry else None
+        a = _host_arrays(_CONTACT_FIELDS, (1, c), R, skip=() if geometry else ("pos", "frame"))
         nt = C.c_int64()
-        rc = self._L.rb_query_contacts(self._h, first, count, R, _lib.ptr(counts), _lib.ptr(partner), _lib.ptr(kind),
-                                       _lib.ptr(dist), _lib.ptr(pos), _lib.ptr(frame), C.byref(nt))
+        rc = self._L.rb_query_contacts(self._h, first, count, R, *(_lib.ptr(v) for v in a.values()), C.byref(nt))
         # (EOVERFLOW / EDOM of a query with valid arguments: a body without a list, every array written)
         if rc != _lib.RB_OK and (strict or rc not in (-75, -33)):
             _lib.check(rc, "rb_query_contacts")
-        return WorldContacts(R, counts, partner, kind, dist, pos, frame, nt.value, first)
+        return WorldContacts(R, *a.values(), nt.value, first)
 
     def query_contacts_device(self, first=0, count=None, max_records=None, geometry=True, dtype=None,
                               out=None) -> WorldContacts:
@@ -383,48 +377,16 @@ class World:
         int32, dist, pos and frame of `dtype` ("f64" / "f32"; None: the
         arrays', else the world's).  truncated is None: nothing is read back,
         and a body without a list shows as -2 in counts alone."""
-        names = ("counts", "partner", "kind", "dist", "pos", "frame")
-        if out is not None:
-            given = {k: (out.get(k) if hasattr(out, "get") else getattr(out, k, None)) for k in names}
-            if given["counts"] is None:
-                raise ValueError("out: counts is required")
-            if given["partner"] is None:
-                R = 0
-            else:
-                try:
-                    R = int(given["partner"].__cuda_array_interface__["shape"][-1])
-                except Exception as exc:
-                    raise TypeError("partner: expected device memory (an object with __cuda_array_interface__), "
-                                    f"got {type(given['partner']).__name__}") from exc
-            if max_records is not None and int(max_records) != R:
-                raise ValueError(f"partner: {R} slots per body, max_records is {int(max_records)}")
-            first, count, _ = self._query_range(first, count, R, geometry)
-        else:
-            given = dict.fromkeys(names)
-            first, count, R = self._query_range(first, count, max_records, geometry)
-        if R < 0:
-            raise ValueError("max_records < 0")
-        ts = _pair_typestr(self.dtype, ("dist", "pos", "frame"), (given["dist"], given["pos"], given["frame"]), dtype)
+        # (with `out` its partner sets R: only first and count are taken here, `bound` is unused)
+        first, count, bound = self._query_range(first, count, max_records if out is None else 0, geometry)
         c = max(count, 0)
-        if out is None:
-            given["counts"] = _new_tensor((1, c), "<i4", self.device)
-            if R > 0:
-                given["partner"] = _new_tensor((1, c, R), "<i4", self.device)
-                given["kind"] = _new_tensor((1, c, R), "<i4", self.device)
-                given["dist"] = _new_tensor((1, c, R), ts, self.device)
-                if geometry:
-                    given["pos"] = _new_tensor((1, c, R, 3), ts, self.device)
-                    given["frame"] = _new_tensor((1, c, R, 3), ts, self.device)
-        shapes = {"counts": ((1, c), ("<i4",)), "partner": ((1, c, R), ("<i4",)), "kind": ((1, c, R), ("<i4",)),
-                  "dist": ((1, c, R), (ts,)), "pos": ((1, c, R, 3), (ts,)), "frame": ((1, c, R, 3), (ts,))}
-        ptrs = {k: None if given[k] is None else _device_array(k, given[k], *shapes[k], out=True)[0] for k in names}
-        if R > 0 and c > 0 and None in (ptrs["partner"], ptrs["kind"], ptrs["dist"]):
-            raise ValueError("partner, kind and dist: all three are required with max_records > 0")
-        _lib.check(self._L.rb_query_contacts_dev(self._h, first, count, R, *(ptrs[k] for k in names), _IO_CODES[ts]),
+        R, ts, given, ptrs = _resolve_out(
+            _CONTACT_FIELDS, (1, c), ("partner", "kind", "dist") if c > 0 else (),
+            "partner, kind and dist: all three are required with max_records > 0", out, max_records, dtype,
+            self.dtype, self.device, lambda: bound, skip=() if geometry else ("pos", "frame"))
+        _lib.check(self._L.rb_query_contacts_dev(self._h, first, count, R, *ptrs.values(), _IO_CODES[ts]),
                    "rb_query_contacts_dev")
-        if R == 0:
-            return WorldContacts(0, given["counts"], None, None, None, None, None, None, first)
-        return WorldContacts(R, *(given[k] for k in names), None, first)
+        return WorldContacts(R, *given.values(), None, first)   # (with R == 0 the library takes counts alone)
 
     def contacts(self):
         """Contact list of the most recent step, CSR over owned bodies:

@@ -10,6 +10,7 @@ the contact kinds the test is about (0 plane-sphere, 1..8 plane-box corner, 16
 sphere-sphere, 17 sphere-box, 32..35 the points of a clipped box-box face, 40
 box-box edge-edge): a state in free flight cannot pass.  The floors were
 checked on the CPU with the oracle and are weaker than what it lists."""
+import ctypes as C
 from collections import Counter
 
 import numpy as np
@@ -248,6 +249,59 @@ def test_counts_only_and_environment_lists(rb, column):
         nogeo = b.contacts(envs=[5], max_records=8, geometry=False)
         assert nogeo.pos is None and nogeo.frame is None
         assert not differing(nogeo, {k: v[[5]] for k, v in d["ref"].items()}, geometry=False)
+
+
+def test_contacts_in_ranges(rb, monkeypatch):
+    """The staging buffer (RBHIP_BATCH_SAMPLE_BYTES, read at creation) sized for
+    two environments: five environments, listed out of order and all at once,
+    take three launches (2, 2, 1) and give every field of the uncut query word
+    for word; one byte short of one environment is RB_EINVAL and writes
+    nothing.  Five replicas of multi_sphere4 with the balls pressed into the
+    ground, each environment to another depth at another place: every
+    environment has contacts and no two have the same rows."""
+    from rbhip import scenes
+    sc = scenes.multi_sphere4()
+    E, M, R = 5, sc.n, 4
+    # one environment's arrays: counts [M] and partner, kind [M][R] int32; dist [M][R], pos and frame [M][R][3] doubles
+    per = 4 * (M + 2 * M * R) + 8 * (M * R + 2 * 3 * M * R)
+    q0, v0 = np.tile(sc.qpos0, (E, 1, 1)), np.zeros((E, M, 6))
+    q0[:, :, 0] += 0.1 * np.arange(E)[:, None]
+    q0[:, :, 2] = 0.1 - 0.002 * (1 + np.arange(E))[:, None]
+    order = [4, 0, 3, 1, 2]
+
+    def uncut_and_state():
+        with rb.BatchWorld(sc, E) as whole:
+            whole.set_state(q0, v0)
+            for _ in range(5):                      # stepped until contacts exist
+                assert whole.step(1) == 0
+                if whole.contacts(max_records=0).counts.min() > 0:
+                    break
+            return whole.contacts(max_records=R), whole.contacts(envs=order, max_records=R), whole.get_state()
+
+    ref, ref_order, (q, v) = uncut_and_state()
+    assert ref.counts.min() > 0 and ref.truncated == 0
+    assert len({_words(ref.dist[e]).tobytes() for e in range(E)}) == E
+    assert not differing(ref_order, {f: getattr(ref, f)[order] for f in FIELDS})
+    monkeypatch.setenv("RBHIP_BATCH_SAMPLE_BYTES", str(2 * per))
+    with rb.BatchWorld(sc, E) as b:
+        b.set_state(q, v)
+        cut = b.contacts(envs=order, max_records=R)
+        assert not differing(cut, {f: getattr(ref_order, f) for f in FIELDS}) and cut.truncated == ref_order.truncated
+        cut = b.contacts(max_records=R)
+        assert not differing(cut, {f: getattr(ref, f) for f in FIELDS}) and cut.truncated == ref.truncated
+    monkeypatch.setenv("RBHIP_BATCH_SAMPLE_BYTES", str(per - 1))
+    with rb.BatchWorld(sc, E) as b:
+        b.set_state(q, v)
+        arrays = [np.full((E, M), 7, np.int32), np.full((E, M, R), 7, np.int32), np.full((E, M, R), 7, np.int32),
+                  np.full((E, M, R), 7.0), np.full((E, M, R, 3), 7.0), np.full((E, M, R, 3), 7.0)]
+        nt = C.c_int64()
+        rc = b._L.rb_batch_contacts(b._h, None, E, R, *(rb._lib.ptr(a) for a in arrays), C.byref(nt))
+        assert rc == EINVAL and b"do not fit the staging buffer" in b._L.rb_last_error()
+        assert all((a == 7).all() for a in arrays)
+        with pytest.raises(rb.RbError) as ei:
+            b.contacts(max_records=R)
+        assert ei.value.code == EINVAL
+        assert np.array_equal(b.contacts(max_records=0).counts, ref.counts)      # (the counts alone fit)
 
 
 # ------------------------------------------------------------ 8. many partners
