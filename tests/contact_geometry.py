@@ -75,7 +75,11 @@ The built ones: plane_diagonal 1,263 of 2,000 (centres on the plane),
 plane_flat 9 of 9, plane_spheres 656 of 1,000, pairs_grazing 1,462 of 1,806
 (fp32: 192, whose band is 1e-4 wide), and none in pairs_coincident,
 cells_lattice, cells_half and cells_period.  1,302 of plane_diagonal's 4,000
-box-plane rows have more than four passing corners.
+box-plane rows have more than four passing corners.  The tile-shaped families
+(TILE_FAMILIES: the broadphase edges thin in z, which the tile form commits):
+none in sheet_lattice (1,100), sheet_negative (406), sheet_period (1,080),
+sheet_radius (1,098) and sheet_piles (1,486), in both precisions;
+sheet_negative and sheet_radius are under the cap.
 
 The tests can fail: of four mutants of the oracle, built apart from the tree,
 three fail tests/test_oracle_contact_geometry.py and the fourth is equivalent
@@ -837,20 +841,150 @@ def radius_mix(n, seed=0):
     return _cloud("radius_mix", np.array(c), r=np.array(r), max_partners=32)
 
 
+# ---- the tile form's broadphase: the same edges, thin in z, so that a tile of
+# x, y columns holds at most 112 bodies and the form commits (tests/tile_fit.py)
+SHEET_TC = (4, 5, 6, 7, 8)
+
+
+def sheet_lattice(n, seed=0):
+    """cells_lattice in a sheet: centres (z = 0) on integer multiples of the
+    column COARSE in x and y, first those on multiples of tc COARSE for every
+    tile width tc = 4 .. 8 at -3 .. +3 tiles about the origin (corners of
+    tiles, on column, tile and slot-row boundaries at once), then random
+    columns within +-24; each with a partner at 2 r (1 -+ 1e-3) in a random,
+    mostly horizontal direction: across a boundary by a hair, or not."""
+    rng = np.random.default_rng(seed)
+    k = np.arange(-3, 4)
+    pts = [np.stack(np.meshgrid(k * tc, k * tc), -1).reshape(-1, 2) for tc in SHEET_TC]
+    pts.append(rng.integers(-24, 25, (n, 2)))
+    c1 = np.concatenate(pts)
+    c1 = c1[np.sort(np.unique(c1, axis=0, return_index=True)[1])][:n // 2]
+    c1 = np.concatenate([c1 * COARSE, np.zeros((len(c1), 1))], 1)
+    sign = np.where(np.arange(len(c1)) % 2 == 0, -1.0, 1.0)
+    d = rng.normal(size=(len(c1), 3)) * [1.0, 1.0, 0.2]
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    c2 = c1 + d * (2 * R0 * (1 + sign * 1e-3))[:, None]
+    pb = _cloud("sheet_lattice", np.stack([c1, c2], 1).reshape(-1, 3))
+    pb.inside = sign < 0
+    return pb
+
+
+def sheet_negative(n, seed=0):
+    """cells_negative as a sheet, twice: one layer on a jittered grid of
+    spacing 0.19 < 2 r with a sparse second layer resting on it (one sphere
+    over every fifth), once entirely in x, y < 0 and once straddling the
+    origin (tiles (-1, -1), (0, -1), (-1, 0) and (0, 0) populated), over a
+    floor and between two walls that face the cloud from the negative side,
+    the lowest bodies resting in them.  Both copies stay within 4 m of the
+    origin (13 x 13 and 34 bodies each at n = 406), where the fp32 residuals of
+    plane records stay under those measured on cells_negative."""
+    rng = np.random.default_rng(seed)
+    side = int(np.sqrt(n / 2 / 1.2))
+    k = np.arange(side * side)
+    base = np.stack([k % side, k // side, np.zeros(len(k))], 1) * [0.19, 0.19, 0.0]
+    c = []
+    for origin in (np.array([-3.8, -3.8, 0.0]), np.array([-0.19 * (side - 1) / 2, -0.19 * (side - 1) / 2, 0.0])):
+        low = origin + base + rng.uniform(-0.02, 0.02, base.shape)
+        top = low[::5] + rng.uniform(-0.03, 0.03, (len(low[::5]), 3)) + [0.0, 0.0, 0.185]
+        c += [low, top]
+    c = np.concatenate(c)[:n]
+    lo = c.min(0)
+    planes = np.array([[[0.0, 0, 1, 0, 0, lo[2] - 0.09], [1.0, 0, 0, lo[0] - 0.09, 0, 0],
+                        [0.0, 1, 0, 0, lo[1] - 0.09, 0]]])
+    return _cloud("sheet_negative", c, planes=planes)
+
+
+def sheet_period(n=0, seed=0, dtype="f64"):
+    """cells_period along x and y only: the clusters offset by COARSE 2^k,
+    k = 0 .. PERIOD_K, along x, along y and along the antidiagonal (2^k,
+    -2^k), a cluster's units on the diagonal columns (3 i, 3 i).  Whatever
+    ntx x nty the fold picks, populated tiles share a slot.  No two units of
+    different clusters share a column (a difference of two shifts is never a
+    multiple of (3, 3) but 0).  31 + 14 clusters of 24 bodies in fp64, 19 + 8
+    of 40 in fp32 (the antidiagonal stops at k = PERIOD_K - 1, which keeps
+    fp32 within 108 m); every body has one record."""
+    K = PERIOD_K[dtype]
+    shifts = [np.zeros(3)] + [np.array(a) * COARSE * 2.0 ** k for a in ((1.0, 0, 0), (0, 1.0, 0)) for k in range(K + 1)]
+    shifts += [np.array([1.0, -1.0, 0]) * COARSE * 2.0 ** k for k in range(K)]     # (k < K: the units reach 5 m further down)
+    t = 2 * R0 * (1 - 1e-3)
+    unit = np.array([[0.05, 0.05, 0.05], [0.05 + t, 0.05, 0.05], [0.05, 0.25, 0.25], [0.05 + t, 0.25, 0.25]])
+    U = PERIOD_UNITS[dtype]
+    cluster = np.concatenate([unit + 3 * i * COARSE * np.array([1.0, 1.0, 0.0]) for i in range(-(U // 2), (U + 1) // 2)])
+    c = np.concatenate([cluster + s for s in shifts])
+    return _cloud("sheet_period", c, expect=np.ones(len(c)))
+
+
+SHEET_BIG = 4 * 4 * 1.001       # a tile of width 4 of the 4-m column that r = 1 sets
+
+
+def sheet_radius(n, seed=0):
+    """radius_mix with the r = 1 spheres a tile of four 4-m columns apart (a
+    5-wide grid about the origin), each with 24 satellites of r = 0.05
+    touching it and 36 hovering 0.02 off it: 61 bodies and 24 partners of one
+    body inside one tile; max_partners 32."""
+    rng = np.random.default_rng(seed)
+    per = 60
+    big = max(1, n // (per + 1))
+    c, r = [], []
+    for b in range(big):
+        centre = np.array([(b % 5 - 1.5) * SHEET_BIG, (b // 5 - 1.5) * SHEET_BIG, 0.0]) + rng.uniform(-.3, .3, 3)
+        c.append(centre)
+        r.append(1.0)
+        for k, d in enumerate(_unit(rng, per)):
+            c.append(centre + d * (1.0 + 0.05 + (0.02 if k >= 24 else -0.002)))
+        r.extend([0.05] * per)
+    return _cloud("sheet_radius", np.array(c), r=np.array(r), max_partners=32)
+
+
+def sheet_piles(n=0, seed=0):
+    """tile_fit.piles: vertical stacks of 7 to 20 spheres in one column,
+    neighbours 2 r (1 - 1e-3) apart, the lowest 1e-3 r deep in the floor
+    z = 0; a few stacks per tile of width 4, some columns with two."""
+    import tile_fit
+    c, expect = tile_fit.piles(seed=seed)
+    return _cloud("sheet_piles", c, planes=np.array([[[0.0, 0, 1, 0, 0, 0.0]]]), expect=expect)
+
+
 PLANE_FAMILIES = {"plane_random": plane_random, "plane_diagonal": plane_diagonal, "plane_flat": plane_flat,
                   "plane_deep": plane_deep, "plane_spheres": plane_spheres}
 PAIR_FAMILIES = {"pairs_random": pairs_random, "pairs_grazing": pairs_grazing, "pairs_coincident": pairs_coincident}
 CELL_FAMILIES = {"cells_lattice": cells_lattice, "cells_half": cells_half, "cells_negative": cells_negative,
                  "cells_period": cells_period, "radius_mix": radius_mix}
-FAMILIES = {**PLANE_FAMILIES, **PAIR_FAMILIES, **CELL_FAMILIES}
-RANDOM_FAMILIES = ("plane_random", "plane_deep", "pairs_random", "cells_negative", "radius_mix", "mixed")
-DTYPE_FAMILIES = ("pairs_grazing", "cells_half", "cells_period")           # built for the precision they run in
+TILE_FAMILIES = {"sheet_lattice": sheet_lattice, "sheet_negative": sheet_negative, "sheet_period": sheet_period,
+                 "sheet_radius": sheet_radius, "sheet_piles": sheet_piles}
+FAMILIES = {**PLANE_FAMILIES, **PAIR_FAMILIES, **CELL_FAMILIES, **TILE_FAMILIES}
+RANDOM_FAMILIES = ("plane_random", "plane_deep", "pairs_random", "cells_negative", "radius_mix", "mixed",
+                   "sheet_negative", "sheet_radius")
+DTYPE_FAMILIES = ("pairs_grazing", "cells_half", "cells_period", "sheet_period")   # built for the precision they run in
+_widths = {}
+
+
+def tile_widths(family, dtype="f64"):
+    """The tile widths at which the family at CASES holds, by tests/tile_fit.py's
+    mirror of the fit: forced to tc the fit keeps tc (the 112 rule does not
+    lower it), no slot holds more than 112 bodies and no window more than 384
+    records.  Nothing is listed by hand: the GPU tests run every width named
+    here, and tests/test_oracle_contact_geometry.py states which ones each
+    family must at least reach."""
+    import tile_fit
+    if (family, dtype) not in _widths:
+        pb = make(family, dtype=dtype)
+        fits = {tc: tile_fit.fit(pb.qpos, column_size(pb), force=tc) for tc in SHEET_TC}
+        _widths[family, dtype] = tuple(tc for tc in SHEET_TC if fits[tc].tc == tc and tile_fit.holds(fits[tc]))
+    return _widths[family, dtype]
 
 # family -> (n, seed) of the CPU tests and of the fp32 measurement
 CASES = {"plane_random": (2000, 0), "plane_diagonal": (2000, 201), "plane_flat": (9, 202), "plane_deep": (1000, 203),
          "plane_spheres": (1000, 204), "pairs_random": (1000, 205), "pairs_grazing": (903, 206),
          "pairs_coincident": (500, 207), "cells_lattice": (1100, 208), "cells_half": (1100, 209),
-         "cells_negative": (1100, 210), "cells_period": (1104, 211), "radius_mix": (1098, 212)}
+         "cells_negative": (1100, 210), "cells_period": (1104, 211), "radius_mix": (1098, 212),
+         "sheet_lattice": (1100, 213), "sheet_negative": (406, 214), "sheet_period": (1080, 215),
+         "sheet_radius": (1098, 216), "sheet_piles": (0, 217)}
+
+
+def column_size(pb):
+    """The column of a world of the problem's bodies (the hashed cell): 4 rmax 1.001."""
+    return 4.0 * float(pb.size[:, 0].max()) * 1.001
 
 
 def make(family, n=None, seed=None, dtype="f64", **kw):

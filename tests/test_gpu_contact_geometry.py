@@ -25,7 +25,12 @@ roll-back.  The form declines the other four: cells_lattice, cells_negative,
 cells_period and radius_mix pack more bodies over one tile of x, y columns
 than a slot steps (they are three-dimensional clouds; the run raises
 TILE_WHY_CAP), the run is rolled back and the world steps hashed; that their
-records are right all the same is asserted too."""
+records are right all the same is asserted too.  Their edges reach the tile
+broadphase through contact_geometry.TILE_FAMILIES, thin in z: each is
+committed at every tile width at which tests/tile_fit.py's mirror of the fit
+says it holds (RBHIP_TILE_COLS; sheet_lattice and sheet_period at 4 .. 8), in
+fp64 and at one width in fp32, with the form, the steps, the width and the
+slot count asserted from the stats."""
 import numpy as np
 import pytest
 
@@ -233,6 +238,38 @@ def test_world_tile_form(rb, oracle, monkeypatch):
     got, st = _world_lists(rb, pb, "f64", steps=2)
     assert st["form"] == 5 and st["tile_rollbacks"] == 0 and st["tile_steps"] == 2, st
     _check_world(pb, ref, want, got, "f64")
+
+
+# every width at which the mirror of the fit says the family holds; in fp32 the middle one of those
+TILE_CASES = [(f, tc) for f in cg.TILE_FAMILIES for tc in cg.tile_widths(f)]
+TILE_F32_WIDTH = {f: cg.tile_widths(f, "f32")[len(cg.tile_widths(f, "f32")) // 2] for f in cg.TILE_FAMILIES}
+
+
+def _tile_family(rb, oracle, monkeypatch, family, tc, dtype):
+    """A tile-shaped family (contact_geometry.TILE_FAMILIES) committed by the
+    tile form at the forced width tc: the grid is the one tests/tile_fit.py's
+    mirror of the fit gives, both steps ran in tile slots, and the records are
+    right by the reference and equal to the oracle's."""
+    import tile_fit
+    _setenv(monkeypatch, {"RBHIP_TILE": "1", "RBHIP_TILE_COLS": str(tc)})     # (read at the fit: set until the steps ran)
+    pb, ref, want = _case(oracle, ("world", family, dtype), lambda: cg.make(family, dtype=dtype), dtype)
+    fit = tile_fit.fit(pb.qpos, cg.column_size(pb), force=tc)
+    assert fit.tc == tc and tile_fit.holds(fit), fit
+    got, st = _world_lists(rb, pb, dtype, steps=2)
+    monkeypatch.delenv("RBHIP_TILE_COLS")
+    assert st["form"] == 5 and st["tile_rollbacks"] == 0 and st["tile_steps"] == 2 and st["tile_why"] == 0, st
+    assert st["tile_cols"] == tc and st["tile_slots"] == fit.slots, (st, fit)
+    _check_world(pb, ref, want, got, dtype)
+
+
+@pytest.mark.parametrize("family,tc", TILE_CASES, ids=[f"{f}-tc{tc}" for f, tc in TILE_CASES])
+def test_world_tile_family(rb, oracle, monkeypatch, family, tc):
+    _tile_family(rb, oracle, monkeypatch, family, tc, "f64")
+
+
+@pytest.mark.parametrize("family", list(cg.TILE_FAMILIES))
+def test_world_tile_family_f32(rb, oracle, monkeypatch, family):
+    _tile_family(rb, oracle, monkeypatch, family, TILE_F32_WIDTH[family], "f32")
 
 
 @pytest.mark.parametrize("family", ["cells_lattice", "cells_negative", "cells_period", "radius_mix"])

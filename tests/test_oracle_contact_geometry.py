@@ -34,6 +34,7 @@ import numpy as np
 import pytest
 
 import contact_geometry as cg
+import tile_fit
 
 FAMILY_IDS = list(cg.FAMILIES)
 
@@ -47,7 +48,7 @@ def family_claims(pb, lists, rep, dtype):
     f, c, cnt, bad = pb.name, rep.counts, lists[0], []
     owner = np.repeat(np.arange(pb.N), cnt)
     partners = np.bincount(owner[lists[1] >= 0], minlength=pb.N)
-    limit = 32 if f == "radius_mix" else 12
+    limit = 32 if f in ("radius_mix", "sheet_radius") else 12
     if partners.max() > limit:
         bad.append(f"a body has {partners.max()} partners (at most {limit})")
     if f == "plane_random" and not (pb.P == cg.MAX_PLANES and c["corner_records"] > 2 * pb.N
@@ -111,6 +112,73 @@ def family_claims(pb, lists, rep, dtype):
         if not (per_cell.max() > 30 and partners.max() >= 20 and pb.max_partners == 32
                 and len(np.unique(pb.size[:, 0])) == 2):
             bad.append(f"radius_mix: {per_cell.max()} bodies in the fullest cell, {partners.max()} partners at most")
+    if f in cg.TILE_FAMILIES:
+        bad += sheet_claims(pb, lists, rep, dtype, partners)
+    return bad
+
+
+def sheet_claims(pb, lists, rep, dtype, partners):
+    """The tile-shaped families: what tests/tile_fit.py's mirror of the fit
+    says the tile form will meet, at every width the family is run at."""
+    f, c, cnt, bad = pb.name, rep.counts, lists[0], []
+    col = cg.column_size(pb)
+    cols = tile_fit.columns(pb.qpos, col)
+    fits = {tc: tile_fit.fit(pb.qpos, col, force=tc) for tc in cg.SHEET_TC}
+    # the widths the GPU tests run are the mirror's (cg.tile_widths); stated here so that a change of a
+    # family that moves them is seen: all five at 4, the lattice and the period at every width; at the
+    # others the 112 rule lowers the forced width (sheet_negative at 5 and 8, sheet_radius from 6 on,
+    # sheet_piles from 5 on)
+    widths = {"sheet_lattice": cg.SHEET_TC, "sheet_negative": (4, 6, 7), "sheet_period": cg.SHEET_TC,
+              "sheet_radius": (4, 5), "sheet_piles": (4,)}[f]
+    if cg.tile_widths(f, dtype) != widths:
+        bad.append(f"{f}: holds at the widths {cg.tile_widths(f, dtype)}, stated {widths}")
+    for tc in cg.SHEET_TC:
+        kept = fits[tc].tc == tc and tile_fit.holds(fits[tc])
+        if kept != (tc in widths) or (not kept and fits[tc].tc >= tc):
+            bad.append(f"{f}: at the forced width {tc}: {fits[tc]}")
+    if f == "sheet_lattice":
+        k = np.round(pb.qpos[0::2, :2] / cg.COARSE).astype(np.int64)          # the centres' lattice points
+        on = np.abs(pb.qpos[0::2, :2] / cg.COARSE - k).max(1) < (1e-9 if dtype == "f64" else 1e-5)   # (9.6 m in fp32: 1e-6 columns)
+        first = np.concatenate([[0], np.cumsum(cnt)])[:-1]
+        listed = np.array([(2 * p + 1) in lists[1][first[2 * p]:first[2 * p] + cnt[2 * p]] for p in range(pb.N // 2)])
+        if not (on.all() and (listed == pb.inside).all()):
+            bad.append(f"sheet_lattice: {int((~on).sum())} centres off the lattice, {int((listed != pb.inside).sum())} partners decided wrongly")
+        for tc in cg.SHEET_TC:
+            t = np.floor_divide(cols, tc)
+            corner = (np.mod(k, tc) == 0).all(1).sum()
+            ax = [int(((t[0::2, a] != t[1::2, a]) & pb.inside).sum()) for a in range(2)]
+            rows = np.mod(t[:, 1], fits[tc].nty)
+            if not (corner >= 49 and min(ax) >= 10 and (t < 0).any(0).all() and ((rows[0::2] != rows[1::2]) & pb.inside).sum() >= 10):
+                bad.append(f"sheet_lattice, width {tc}: {corner} centres on tile corners, touching pairs across a tile boundary per axis {ax}")
+    if f == "sheet_negative":
+        tiles = set(map(tuple, np.floor_divide(cols, 4).tolist()))
+        half = pb.N // 2
+        planes_hit = set(lists[1][lists[1] < 0].tolist())
+        if not ({(-1, -1), (0, -1), (-1, 0), (0, 0)} <= tiles and (pb.qpos[:half, :2] < 0).all() and (np.floor_divide(cols[:half], 4) < 0).all()
+                and c["sphere_pairs"] > pb.N and planes_hit == {-1, -2, -3} and fits[4].worst_column > tile_fit.WR):
+            bad.append(f"sheet_negative: {c['sphere_pairs']} pairs, planes {planes_hit}, tiles about the origin "
+                       f"{sorted(t for t in tiles if max(map(abs, t)) <= 1)}")
+    if f == "sheet_period":
+        far = [(cols[:, a] > 2 ** 10).sum() for a in range(2)] + [(cols[:, 1] < -2 ** 10).sum()]
+        want = 2 if dtype == "f64" else 0
+        if not (all(x >= want * 24 for x in far) and c["sphere_pairs"] == pb.N // 2 and np.abs(pb.qpos[:, 2]).max() < 0.3):
+            bad.append(f"sheet_period: bodies past 2^10 columns {far}, {c['sphere_pairs']} pairs")
+        for tc in cg.SHEET_TC:
+            if not (fits[tc].folded and fits[tc].aliased >= 2):
+                bad.append(f"sheet_period, width {tc}: {fits[tc].aliased} populated tiles share a slot: {fits[tc]}")
+    if f == "sheet_radius":
+        big = pb.size[:, 0] == 1.0
+        tiles = np.floor_divide(cols[big], 4)
+        if not (len(np.unique(tiles, axis=0)) == big.sum() and (partners[big] == 24).all() and partners.max() == 24
+                and pb.max_partners == 32 and fits[4].worst_column > 12):
+            bad.append(f"sheet_radius: {len(np.unique(tiles, axis=0))} tiles for {big.sum()} big spheres, partners {partners[big].tolist()}")
+    if f == "sheet_piles":
+        ring = fits[4].window_cols.copy()
+        ring[:, :, 1:-1, 1:-1] = 0
+        per_column = np.unique(cols, axis=0, return_counts=True)[1]
+        if not (fits[4].worst_column > 12 and (fits[4].cols > tile_fit.WR).sum() >= 50 and ring.max() > 12
+                and 7 <= per_column.min() and (cnt == pb.expect).all()):
+            bad.append(f"sheet_piles: the fullest column holds {fits[4].worst_column}, the fullest ring column {ring.max()}")
     return bad
 
 
