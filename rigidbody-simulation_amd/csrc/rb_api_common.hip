@@ -124,6 +124,28 @@ int grow(void **buf, size_t *cap, size_t need) {
     return RB_OK;
 }
 
+void DevMem::reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+}
+int DevMem::alloc_uncached(size_t n) {
+    reset();
+    HIPCHK(hipExtMallocWithFlags(&p, n, hipDeviceMallocUncached));
+    bytes = n;
+    return RB_OK;
+}
+void HostMem::reset() {
+    if (p) (void)hipHostFree(p);
+    p = d = nullptr;
+}
+int HostMem::alloc(size_t n, unsigned flags) {
+    reset();
+    HIPCHK(hipHostMalloc(&p, n, flags));
+    if (flags & hipHostMallocMapped) HIPCHK(hipHostGetDevicePointer(&d, p, 0));
+    return RB_OK;
+}
+
 int dev_ptrs(int device, const char *owner, std::initializer_list<std::pair<const void *, const char *>> arrays) {
     for (const auto &[p, name] : arrays) {
         if (!p) continue;

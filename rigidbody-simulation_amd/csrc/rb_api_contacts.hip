@@ -40,28 +40,25 @@ static int query_supported(const rb_world *w) {
     return RB_OK;
 }
 
-// the layout word without the period's split: refits move the split only, and
-// what is left decides where a bucket's header lies in the lines
-static int32_t layout_key(const rb_world *w) { return w->group & ~(0xfff << 12); }
-
 // The query's table for the world's grid as it stands.  A table of another
 // size or line layout is dropped (table growth): headers of the old layout
-// would be read as ids, and ids as headers.
+// would be read as ids, and ids as headers.  (The layout word without the
+// period's split, layout_key: refits move the split only, and what is left
+// decides where a bucket's header lies in the lines.)
 static int query_table(rb_world *w) {
-    const size_t lines = sizeof(uint32_t) * LINE_WORDS * (size_t)w->H, spill = sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES;
-    if (w->cq_line && (w->cq_H != w->H || w->cq_layout != layout_key(w))) {
+    const size_t lines = line_bytes(w->H), spill = spill_bytes;
+    if (w->cq_line && (w->cq_H != w->H || w->cq_layout != layout_key(w->group))) {
         HIPCHK(hipStreamSynchronize(w->stream));     // (a query in flight reads it)
-        HIPCHK(hipFree(w->cq_line));
-        w->cq_line = nullptr;
+        w->cq_line.reset();
     }
     if (!w->cq_line) {
-        HIPCHK(hipMalloc((void **)&w->cq_line, lines));
+        WCHK(w->cq_line.alloc(lines));
         w->cq_H = w->H;
-        w->cq_layout = layout_key(w);
+        w->cq_layout = layout_key(w->group);
         w->cq_gen = 0;
     }
-    if (!w->cq_spill) HIPCHK(hipMalloc((void **)&w->cq_spill, spill));
-    if (!w->cq_words) HIPCHK(hipMalloc((void **)&w->cq_words, sizeof(uint32_t) * 2));
+    if (!w->cq_spill) WCHK(w->cq_spill.alloc(spill));
+    if (!w->cq_words) WCHK(w->cq_words.alloc(sizeof(uint32_t) * 2));
     // headers of generation 0 are empty buckets: a new table, and one whose
     // generations are used up, starts from zeros
     if (w->cq_gen == 0 || w->cq_gen == UINT32_MAX) {
@@ -139,12 +136,10 @@ static int query_launch(rb_world *w, int64_t first, int64_t count, int32_t R, in
 static int stage_reserve(rb_world *w, size_t bytes) {
     if (bytes <= w->cq_stage_bytes) return RB_OK;
     HIPCHK(hipStreamSynchronize(w->stream));
-    if (w->cq_stage_h) { HIPCHK(hipHostFree(w->cq_stage_h)); w->cq_stage_h = nullptr; }
-    size_t cap = 0;
     w->cq_stage_bytes = 0;
-    WCHK(grow((void **)&w->cq_stage, &cap, bytes));
-    HIPCHK(hipHostMalloc((void **)&w->cq_stage_h, bytes, hipHostMallocDefault));
-    w->cq_stage_bytes = cap;
+    WCHK(w->cq_stage.alloc(bytes));
+    WCHK(w->cq_stage_h.alloc(bytes, hipHostMallocDefault));
+    w->cq_stage_bytes = bytes;
     return RB_OK;
 }
 

@@ -12,9 +12,9 @@ static int kat_common(int32_t device, int32_t dtype, int64_t n, const double *in
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RB_ENODEV, "no HIP device available");
     HIPCHK(hipSetDevice(device));
-    double *din = nullptr, *dout = nullptr;
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin * n));
-    if (hipMalloc(&dout, sizeof(double) * nout * n) != hipSuccess) { (void)hipFree(din); return fail(RB_ENOMEM, "hipMalloc"); }
+    DevBuf<double> din, dout;
+    WCHK(din.alloc(sizeof(double) * nin * n));
+    WCHK(dout.alloc(sizeof(double) * nout * n));
     hipError_t e = hipMemcpy(din, in, sizeof(double) * nin * n, hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = by_real(dtype, [&](auto t) {
@@ -26,8 +26,6 @@ static int kat_common(int32_t device, int32_t dtype, int64_t n, const double *in
                                 : launch_kat_impulse<T>(n, din, dout, nullptr);
         });
     if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * nout * n, hipMemcpyDeviceToHost);
-    (void)hipFree(din);
-    (void)hipFree(dout);
     HIPCHK(e);
     return RB_OK;
 }

@@ -67,8 +67,8 @@ template <typename T> HaloParams<T> make_halo(rb_world *w, int64_t c, int nsp) {
     hp.push_cnt = w->push_cnt;
     hp.halo_e = w->halo_e;
     hp.own = dp<Snap<T>>(w->snap[c % 2], 0);
-    hp.peer_mail = reinterpret_cast<char *const *>(w->peer_flags_dev);
-    hp.mail = reinterpret_cast<const char *>(w->flags);
+    hp.peer_mail = reinterpret_cast<char *const *>(w->peer_flags_dev.get());
+    hp.mail = reinterpret_cast<const char *>(w->flags.get());
     hp.lay = MailLayout::make(w->P, w->S, w->esz, w->boxes);
     hp.epoch = w->epoch;
     hp.rank = (int32_t)w->rank;
@@ -87,7 +87,7 @@ int rccl_gather(rb_world *w, int sp, hipStream_t s) {
     const size_t n = (size_t)4 * w->S;
     const ncclDataType_t ty = w->dtype == RB_F64 ? ncclFloat64 : ncclFloat32;
     for (int k = 0; k < (w->boxes ? 2 : 1); ++k) {
-        char *buf = static_cast<char *>(k == 0 ? w->snap[sp] : w->qsnap[sp]);
+        char *buf = static_cast<char *>(k == 0 ? w->snap[sp].get() : w->qsnap[sp].get());
         const ncclResult_t r = rccl().AllGather(buf + (size_t)w->esz * n * w->rank, buf, n, ty, w->comm, s);
         if (r != ncclSuccess) return fail(RB_ENODEV, "ncclAllGather: %s", rccl().GetErrorString(r));
     }
@@ -110,7 +110,7 @@ int p2p_nhandles(const rb_world *w) { return w->boxes ? 5 : 3; }
 // both parities of the own cell bounds empty: the next step kernel folds
 // into one, the exchange after it resets the other
 int reset_bounds(rb_world *w) {
-    if (!w->bounds) HIPCHK(hipMalloc((void **)&w->bounds, sizeof(int32_t) * 2 * BOUND_COPIES * BOUND_STRIDE));
+    if (!w->bounds) WCHK(w->bounds.alloc(sizeof(int32_t) * 2 * BOUND_COPIES * BOUND_STRIDE));
     std::vector<int32_t> b((size_t)2 * BOUND_COPIES * BOUND_STRIDE, 0);
     for (int k = 0; k < 2 * BOUND_COPIES; ++k)
         for (int d = 0; d < 3; ++d) { b[(size_t)k * BOUND_STRIDE + d] = INT32_MAX; b[(size_t)k * BOUND_STRIDE + 3 + d] = INT32_MIN; }
@@ -156,14 +156,10 @@ int halo_prime(rb_world *w) {
     return RB_OK;
 }
 
-// a world's communicator, peer mappings and exchange buffers (free_world)
+// a world's communicator and peer mappings (free_world; the exchange buffers go with the world)
 void shard_release(rb_world *w) {
     if (w->comm) (void)rccl().CommDestroy(w->comm);
     for (void *q : w->ipc_opened) (void)hipIpcCloseMemHandle(q);
-    void *p2pbufs[] = {w->flags, w->epoch, w->peer_snap_dev, w->peer_quat_dev, w->peer_flags_dev, w->bounds, w->push_cnt,
-                       w->halo_e};
-    for (void *b : p2pbufs)
-        if (b) (void)hipFree(b);
 }
 
 }  // namespace rb::host
@@ -254,7 +250,7 @@ int rb_p2p_handles(rb_world *w, void *out, int64_t cap, int64_t *len) {
         // the mailbox, uncached: peers write it over xGMI while this rank's
         // kernels poll and read it
         const MailLayout lay = MailLayout::make(w->P, w->S, w->esz, w->boxes);
-        HIPCHK(hipExtMallocWithFlags((void **)&w->flags, (size_t)lay.bytes, hipDeviceMallocUncached));
+        WCHK(w->flags.alloc_uncached((size_t)lay.bytes));
         WCHK(wfill(w, w->flags, 0, (size_t)lay.bytes));
         HIPCHK(hipStreamSynchronize(w->stream));     // (the peers map it next)
     }
@@ -306,12 +302,12 @@ int rb_p2p_connect(rb_world *w, const void *all, int64_t len) {
         quats[(size_t)(w->P + q)] = ptr[4];
     }
     if (w->boxes) {
-        HIPCHK(hipMalloc((void **)&w->peer_quat_dev, sizeof(void *) * quats.size()));
+        WCHK(w->peer_quat_dev.alloc(sizeof(void *) * quats.size()));
         WCHK(wput(w, w->peer_quat_dev, quats.data(), sizeof(void *) * quats.size()));
     }
-    HIPCHK(hipMalloc((void **)&w->peer_snap_dev, sizeof(void *) * snaps.size()));
-    HIPCHK(hipMalloc((void **)&w->peer_flags_dev, sizeof(int64_t *) * flags.size()));
-    HIPCHK(hipMalloc((void **)&w->epoch, sizeof(int64_t)));
+    WCHK(w->peer_snap_dev.alloc(sizeof(void *) * snaps.size()));
+    WCHK(w->peer_flags_dev.alloc(sizeof(int64_t *) * flags.size()));
+    WCHK(w->epoch.alloc(sizeof(int64_t)));
     WCHK(wput(w, w->peer_snap_dev, snaps.data(), sizeof(void *) * snaps.size()));
     WCHK(wput(w, w->peer_flags_dev, flags.data(), sizeof(int64_t *) * flags.size()));
     WCHK(wfill(w, w->epoch, 0, sizeof(int64_t)));
@@ -331,8 +327,8 @@ int rb_p2p_halo(rb_world *w, int32_t enable) {
     HIPCHK(hipSetDevice(w->device));
     HIPCHK(hipStreamSynchronize(w->stream));
     if (enable) {
-        if (!w->push_cnt) HIPCHK(hipMalloc((void **)&w->push_cnt, sizeof(int32_t) * w->P));
-        if (!w->halo_e) HIPCHK(hipMalloc((void **)&w->halo_e, sizeof(int64_t)));
+        if (!w->push_cnt) WCHK(w->push_cnt.alloc(sizeof(int32_t) * w->P));
+        if (!w->halo_e) WCHK(w->halo_e.alloc(sizeof(int64_t)));
         if (int rc = reset_bounds(w)) return rc;
         WCHK(wfill(w, w->push_cnt, 0, sizeof(int32_t) * w->P));
     }

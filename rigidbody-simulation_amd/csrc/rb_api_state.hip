@@ -11,12 +11,10 @@ static int io_alloc(rb_world *w) {
     const size_t nq = (size_t)7 * w->N, nv = (size_t)6 * w->N;
     // mapped and coherent: rb_get_state's kernel stores into them across
     // PCIe, visible to the host once the stream is synchronised
-    HIPCHK(hipHostMalloc((void **)&w->io_q_h, sizeof(double) * nq, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostMalloc((void **)&w->io_v_h, sizeof(double) * nv, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer((void **)&w->io_q_hd, w->io_q_h, 0));
-    HIPCHK(hipHostGetDevicePointer((void **)&w->io_v_hd, w->io_v_h, 0));
-    HIPCHK(hipMalloc((void **)&w->io_q_d, sizeof(double) * nq));
-    HIPCHK(hipMalloc((void **)&w->io_v_d, sizeof(double) * nv));
+    WCHK(w->io_q_h.alloc(sizeof(double) * nq, hipHostMallocMapped | hipHostMallocCoherent));
+    WCHK(w->io_v_h.alloc(sizeof(double) * nv, hipHostMallocMapped | hipHostMallocCoherent));
+    WCHK(w->io_q_d.alloc(sizeof(double) * nq));
+    WCHK(w->io_v_d.alloc(sizeof(double) * nv));
     return RB_OK;
 }
 
@@ -53,11 +51,11 @@ template <typename T> static StateIO<T> make_io(rb_world *w) {
 // 128 x 256 grid (17.9 -> 13.2 us).  Deterministic in the global positions,
 // so every rank of a sharded world picks the same split.
 void fit_period(rb_world *w, const double *qpos, bool force) {
-    if (!((w->group >> 24) & 1)) return;                 // hashed layouts have no period
+    if (!layout_linear(w->group)) return;                 // hashed layouts have no period
     if (const char *ev = getenv("RBHIP_FIT_PERIOD"))
         if (atoi(ev) == 0) return;                       // diagnostic: keep the creation-time split
-    const int gb[3] = {w->group & 15, (w->group >> 4) & 15, (w->group >> 8) & 15};
-    const int lg = ((w->group >> 12) & 15) + ((w->group >> 16) & 15) + ((w->group >> 20) & 15);
+    const int gb[3] = {shape_bits(w->group, 0), shape_bits(w->group, 1), shape_bits(w->group, 2)};
+    const int lg = period_bits(w->group);
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     std::vector<int64_t> occ;
     occ.reserve((size_t)w->N);
@@ -94,9 +92,9 @@ void fit_period(rb_world *w, const double *qpos, bool force) {
     double need[3];
     for (int d = 0; d < 3; ++d)
         need[d] = hi[d] >= lo[d] ? (floor(hi[d]) - floor(lo[d]) + 2) / double(1 << gb[d]) : 1.0;
-    int best[3] = {(w->group >> 12) & 15, (w->group >> 16) & 15, (w->group >> 20) & 15};
+    int best[3] = {period_bits(w->group, 0), period_bits(w->group, 1), period_bits(w->group, 2)};
     best_period_split(PeriodSet(std::move(occ)), need, lg, best);
-    const int32_t g = (w->group & ~(0xfff << 12)) | (best[0] << 12) | (best[1] << 16) | (best[2] << 20);
+    const int32_t g = with_period(w->group, best[0], best[1], best[2]);
     if (g != w->group) {
         w->group = g;
         drop_graphs(w);                                  // the grid is a captured kernel argument
@@ -169,8 +167,8 @@ int rb_get_state(rb_world *w, double *qpos, double *qvel) {
         HIPCHK(by_real(w->dtype, [&](auto t) {
             using T = decltype(t);
             StateIO<T> p = make_io<T>(w);
-            p.qpos = w->io_q_hd;
-            p.qvel = w->io_v_hd;
+            p.qpos = w->io_q_h.dev();
+            p.qvel = w->io_v_h.dev();
             return launch_state_out_flat<T>(p, qpos, qvel, w->stream);
         }));
         HIPCHK(hipStreamSynchronize(w->stream));

@@ -1,6 +1,6 @@
 // rb_api_step.hip — stepping: the step kernels' parameters, the table's
-// prime, the captured-graph cache, guarded chunks with their roll-back,
-// refit and growth, and rb_step / rb_step_async / rb_sync.
+// prime, the captured-graph cache, the chunks of a run (the guarded ones:
+// rb_api_guard.hip), and rb_step / rb_step_async / rb_sync.
 #include "rb_host.hpp"
 
 namespace rb::host {
@@ -58,8 +58,8 @@ template <typename T> StepParams<T> make_step(rb_world *w, int64_t c, double dt,
     p.epoch = w->p2p ? w->epoch : nullptr;
     p.bounds = w->p2p ? w->bounds + (c % 2) * BOUND_COPIES * BOUND_STRIDE : nullptr;   // (peer-to-peer: both modes filter by them)
     if (w->p2p && w->halo) {                     // the step kernels push to the peers (rb_halo.hpp)
-        p.halo.peer_mail = reinterpret_cast<char *const *>(w->peer_flags_dev);
-        p.halo.mail = reinterpret_cast<const char *>(w->flags);
+        p.halo.peer_mail = reinterpret_cast<char *const *>(w->peer_flags_dev.get());
+        p.halo.mail = reinterpret_cast<const char *>(w->flags.get());
         p.halo.push_cnt = w->push_cnt;
         p.halo.halo_e = w->halo_e;
         p.halo.lay = MailLayout::make(w->P, w->S, w->esz, w->boxes);
@@ -178,9 +178,9 @@ static int read_err(rb_world *w) {
     // the word reaches pinned host memory through publish_err_kernel: at the
     // end of the last graph, or enqueued here when other error-writing work
     // followed it (a separate launch costs ~9 us at a sync)
-    if (!w->err_pub) HIPCHK(launch_publish_err(w->err, w->err_host_d, w->stream));
+    if (!w->err_pub) HIPCHK(launch_publish_err(w->err, w->err_host.dev(), w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
-    const int32_t bits = __atomic_load_n(w->err_host, __ATOMIC_ACQUIRE);
+    const int32_t bits = __atomic_load_n(w->err_host.get(), __ATOMIC_ACQUIRE);
     if (bits) {
         w->err_pub = false;
         HIPCHK(hipMemsetAsync(w->err, 0, sizeof(int32_t), w->stream));
@@ -248,141 +248,21 @@ int gen_guard(rb_world *w, int64_t nsteps) {
                                   "the sharded world must be recreated");
     HIPCHK(hipStreamSynchronize(w->stream));
     for (int k = 0; k < 2; ++k) {
-        WCHK(wfill(w, w->ids[k], 0, sizeof(uint32_t) * LINE_WORDS * w->H));
-        WCHK(wfill(w, w->spill[k], 0, sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES));
+        WCHK(wfill(w, w->ids[k], 0, line_bytes(w->H)));
+        WCHK(wfill(w, w->spill[k], 0, spill_bytes));
     }
     w->gen_off = 1u - (uint32_t)w->c;   // prime() makes step c's generation 2
     w->primed = false;
     return RB_OK;
 }
 
-// Guarded chunks (enqueue_steps): the chunk-start copy (state rows,
-// snapshot, box orientations, error word), the check after the chunk (error
-// word, deferral counts: one host sync), the roll-back.
-constexpr int64_t GUARD_MIN_STEPS = 64;   // shorter synchronous calls are not guarded (their
-                                          // save + check would cost a few % of the call)
-static size_t chunk_save_bytes(const rb_world *w) {
-    return (size_t)w->esz * (13 * (size_t)w->S + 8 * (size_t)w->Npad) + sizeof(int32_t);
-}
-static int chunk_save(rb_world *w) {
-    if (!w->opt_save) {
-        HIPCHK(hipMalloc(&w->opt_save, chunk_save_bytes(w)));
-        HIPCHK(hipHostMalloc((void **)&w->defer_host, sizeof(int32_t) * 4, 0));
-    }
-    char *o = static_cast<char *>(w->opt_save);
-    const size_t st = (size_t)w->esz * 13 * w->S, sn = (size_t)w->esz * 4 * w->Npad;
-    HIPCHK(hipMemcpyAsync(o, w->state, st, hipMemcpyDeviceToDevice, w->stream));
-    HIPCHK(hipMemcpyAsync(o + st, w->snap[w->sp()], sn, hipMemcpyDeviceToDevice, w->stream));
-    if (w->boxes) HIPCHK(hipMemcpyAsync(o + st + sn, w->qsnap[w->sp()], sn, hipMemcpyDeviceToDevice, w->stream));
-    HIPCHK(hipMemcpyAsync(o + st + 2 * sn, w->err, sizeof(int32_t), hipMemcpyDeviceToDevice, w->stream));
-    // the error bits from before the chunk (an earlier rb_step_async), read with the check
-    HIPCHK(hipMemcpyAsync(w->defer_host + 3, w->err, sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
-    if (w->boxes) HIPCHK(hipMemsetAsync(w->defer_cnt, 0, sizeof(int32_t) * 2, w->stream));
-    return RB_OK;
-}
-static int chunk_check(rb_world *w, int32_t &err, bool &deferred) {
-    HIPCHK(hipMemcpyAsync(w->defer_host, w->err, sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
-    if (w->boxes) HIPCHK(hipMemcpyAsync(w->defer_host + 1, w->defer_cnt, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, w->stream));
-    HIPCHK(hipStreamSynchronize(w->stream));
-    err = w->defer_host[0] & ~w->defer_host[3];       // raised during this chunk
-    if (w->diag_overflow > 0) { --w->diag_overflow; err |= ERR_BUCKET_OVERFLOW; }
-    deferred = w->boxes && (w->defer_host[1] | w->defer_host[2]) != 0;
-    return RB_OK;
-}
-static int chunk_restore(rb_world *w) {
-    const char *o = static_cast<const char *>(w->opt_save);
-    const size_t st = (size_t)w->esz * 13 * w->S, sn = (size_t)w->esz * 4 * w->Npad;
-    HIPCHK(hipMemcpyAsync(w->state, o, st, hipMemcpyDeviceToDevice, w->stream));
-    HIPCHK(hipMemcpyAsync(w->snap[w->sp()], o + st, sn, hipMemcpyDeviceToDevice, w->stream));
-    if (w->boxes) HIPCHK(hipMemcpyAsync(w->qsnap[w->sp()], o + st + sn, sn, hipMemcpyDeviceToDevice, w->stream));
-    w->err_pub = false;
-    HIPCHK(hipMemcpyAsync(w->err, o + st + 2 * sn, sizeof(int32_t), hipMemcpyDeviceToDevice, w->stream));
-    if (w->boxes) HIPCHK(hipMemsetAsync(w->defer_cnt, 0, sizeof(int32_t) * 2, w->stream));
-    w->primed = false;
-    w->tile_valid_sp = -1;
-    return RB_OK;
-}
-// twice the buckets (both tables, emptied), if under the world's limit; the
-// linear layout's period gets the extra bit (refit_from_device re-splits it)
-static int grow_table(rb_world *w, bool &grown) {
-    grown = false;
-    if (w->H * 2 > w->hmax) return RB_OK;
-    HIPCHK(hipStreamSynchronize(w->stream));
-    drop_graphs(w);                                   // H and the grid are captured kernel arguments
-    const int64_t H = w->H * 2;
-    for (int k = 0; k < 2; ++k) {
-        HIPCHK(hipFree(w->ids[k]));
-        w->ids[k] = nullptr;
-        HIPCHK(hipMalloc((void **)&w->ids[k], sizeof(uint32_t) * LINE_WORDS * H));
-        WCHK(wfill(w, w->ids[k], 0, sizeof(uint32_t) * LINE_WORDS * H));
-        if (w->pos[k]) {
-            HIPCHK(hipFree(w->pos[k]));
-            w->pos[k] = nullptr;
-            HIPCHK(hipMalloc(&w->pos[k], (size_t)w->esz * 4 * LINE_WORDS * H));
-        }
-    }
-    w->H = H;
-    if ((w->group >> 24) & 1) {
-        const int lx = (w->group >> 12) & 15, ly = (w->group >> 16) & 15;
-        w->group += lx < 15 ? (1 << 12) : ly < 15 ? (1 << 16) : (1 << 20);
-    }
-    w->fit_valid = false;
-    w->primed = false;
-    w->table_grows += 1;
-    grown = true;
-    return RB_OK;
-}
-
-// max_partners raised to 32 (the second kernel instantiation), contact
-// records resized to match
-static int grow_partners(rb_world *w) {
-    HIPCHK(hipStreamSynchronize(w->stream));
-    drop_graphs(w);                                   // the instantiation is chosen at capture
-    w->maxp = 32;
-    w->maxrec = 4 * w->n_planes + (w->boxes ? 4 : 1) * w->maxp;
-    if (w->rec_count) {
-        const size_t slots = (size_t)w->maxrec * (w->S > 0 ? w->S : 1);
-        void *old[] = {w->rec_partner, w->rec_kind, w->rec_dist};
-        for (void *b : old) HIPCHK(hipFree(b));
-        w->rec_partner = nullptr; w->rec_kind = nullptr; w->rec_dist = nullptr;
-        HIPCHK(hipMalloc((void **)&w->rec_partner, sizeof(int32_t) * slots));
-        HIPCHK(hipMalloc((void **)&w->rec_kind, sizeof(int32_t) * slots));
-        HIPCHK(hipMalloc(&w->rec_dist, (size_t)w->esz * slots));
-    }
-    w->partner_grows += 1;
-    return RB_OK;
-}
-
-// the current snapshot's first N rows (x, y, z, bound radius) on the host, as doubles
-int snapshot_to_host(rb_world *w, std::vector<double> &rows) {
-    rows.resize((size_t)4 * w->N);
-    return by_real(w->dtype, [&](auto t) -> int {
-        using T = decltype(t);
-        std::vector<T> sn(rows.size());
-        HIPCHK(hipMemcpyAsync(sn.data(), w->snap[w->sp()], sizeof(T) * sn.size(), hipMemcpyDeviceToHost, w->stream));
-        HIPCHK(hipStreamSynchronize(w->stream));
-        std::copy(sn.begin(), sn.end(), rows.begin());
-        return RB_OK;
-    });
-}
-
-// the layout period refitted to the current positions (the snapshot, read
-// back once: waits for the stream); force: fit_period's
-int refit_from_device(rb_world *w, bool force) {
-    std::vector<double> sn, q((size_t)7 * w->N, 0.0);
-    WCHK(snapshot_to_host(w, sn));
-    for (int64_t b = 0; b < w->N; ++b)
-        for (int d = 0; d < 3; ++d) q[(size_t)(7 * b + d)] = sn[(size_t)(4 * b + d)];
-    fit_period(w, q.data(), force);
-    return RB_OK;
-}
 // ---- captured step graphs ---------------------------------------------------
 // A sequence of launches covering K steps from step c0 (`seq(stream, c0)`),
 // captured once per start parity and replayed (rb_world::graphs, keyed by the
 // step count, parity, step parameters and variant).
 int graph_replay(rb_world *w, int64_t K, int variant, double dt, double e, double mu, double thr,
                  const std::function<int(hipStream_t, int64_t)> &seq) {
-    const bool tile_graph = (variant & 16) && w->tile_pub_host_d;   // (a tile run's: its words too)
+    const bool tile_graph = (variant & 16) && w->tile_pub_host;   // (a tile run's: its words too)
     auto key = std::make_tuple(K, (int)(w->c % 2), dt, e, mu, thr, variant);
     auto it = w->graphs.find(key);
     if (it == w->graphs.end()) {
@@ -402,9 +282,9 @@ int graph_replay(rb_world *w, int64_t K, int variant, double dt, double e, doubl
             HIPCHK(hipStreamBeginCapture(w->cap_stream, hipStreamCaptureModeThreadLocal));
             int rc = seq(w->cap_stream, c0);
             const hipError_t pe = rc ? hipSuccess
-                                     : tile_graph ? launch_publish_err(w->err, w->err_host_d, w->cap_stream, w->tile_why,
-                                                                       w->tile_commits, w->tile_pub_host_d)
-                                                  : launch_publish_err(w->err, w->err_host_d, w->cap_stream);
+                                     : tile_graph ? launch_publish_err(w->err, w->err_host.dev(), w->cap_stream, w->tile_why,
+                                                                       w->tile_commits, w->tile_pub_host.dev())
+                                                  : launch_publish_err(w->err, w->err_host.dev(), w->cap_stream);
             if (rc || pe != hipSuccess) {
                 (void)hipStreamEndCapture(w->cap_stream, &graph);
                 if (rc) return rc;
@@ -499,65 +379,9 @@ int enqueue_steps(rb_world *w, int64_t nsteps, double dt, double e, double mu, d
         // chunks of a synchronous call (rb_step), whose broadphase layout is
         // refitted if the scene drifted out of it (a bucket overflowed)
         const bool guard = opt || (w->sync_call && K >= GUARD_MIN_STEPS && solo && w->law == RB_LAW_MUJOCO);
-        if (!guard) {
-            if (int rc = replay(K, variant)) return rc;
-            w->c += K;
-            left -= K;
-            continue;
-        }
-        bool refitted = false;
-        for (;;) {
-            if (int rc = chunk_save(w)) return rc;
-            w->box_kernel_on = !opt;
-            const int rc = replay(K, variant | (opt ? 4 : 0));
-            w->box_kernel_on = true;
-            if (rc) return rc;
-            int32_t err = 0;
-            bool deferred = false;
-            if (int rc2 = chunk_check(w, err, deferred)) return rc2;
-            if (opt) w->box_stats[0] += 1;
-            // bucket overflow right after a fit of one step: a real overflow
-            // (reported by the caller's error check)
-            const bool overflow = (err & ERR_BUCKET_OVERFLOW) && !(refitted && K == 1);
-            // more sphere partners than max_partners 16: the 32-partner kernels
-            const bool partners = (err & ERR_PARTNER_OVERFLOW) && w->maxp < 32;
-            deferred = deferred && opt;
-            if (!overflow && !deferred && !partners) {
-                if (opt && w->box_backoff > 0) w->box_backoff /= 2;
-                break;
-            }
-            if (int rc3 = chunk_restore(w)) return rc3;
-            if (deferred) {
-                // a box-involved pair came into range: the chunk again, from
-                // its start, with the box kernel; the next chunks keep it
-                w->box_stats[1] += 1;
-                w->box_backoff = w->box_backoff ? std::min(2 * w->box_backoff, 64) : 1;
-                w->box_skip = w->box_backoff;
-                opt = false;
-            }
-            if (partners)
-                if (int rc3 = grow_partners(w)) return rc3;
-            if (overflow) {
-                // the scene outgrew the layout it was fitted for: refit to
-                // the chunk-start positions; if the chunk overflows again,
-                // a table twice the size (one more period bit), and once the
-                // table is at its limit, shorter chunks
-                if (refitted) {
-                    bool grown = false;
-                    if (int rc3 = grow_table(w, grown)) return rc3;
-                    if (!grown) K = K > 1 ? K / 2 : 1;
-                }
-                if (int rc3 = refit_from_device(w)) return rc3;
-                w->refits += 1;
-                refitted = true;
-            }
-            // table headers only rise (atomicMax on generation): the
-            // replay's generations must lie above every one the rolled-
-            // back chunk used
-            w->gen_off += (uint32_t)K + 1u;
-            if (int rc3 = gen_guard(w, left + K)) return rc3;
-            if (int rc3 = prime(w, dt, e, mu)) return rc3;
-        }
+        const int rc = !guard ? replay(K, variant)
+                              : guarded_chunk(w, K, left, opt, dt, e, mu, [&](int64_t k, bool o) { return replay(k, variant | (o ? 4 : 0)); });
+        if (rc) return rc;
         w->c += K;
         left -= K;
     }

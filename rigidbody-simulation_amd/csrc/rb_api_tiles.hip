@@ -77,7 +77,7 @@ static size_t tile_bins_bytes(const rb_world *w) {
 }
 template <typename T> static TileBins<T> tile_bins(const rb_world *w, int sp) {
     const size_t slots = (size_t)w->tile_ntx * w->tile_nty, cap = (size_t)w->tile_cap;
-    char *b = static_cast<char *>(w->tile_mem) + (size_t)sp * tile_bins_bytes(w);
+    char *b = static_cast<char *>(w->tile_mem.get()) + (size_t)sp * tile_bins_bytes(w);
     TileBins<T> t;
     t.off = reinterpret_cast<int32_t *>(b);
     b += slots * TILE_OFFW * 4;
@@ -105,14 +105,13 @@ constexpr size_t TILE_AUTO_MAX_BYTES_PER_BODY = 2048;   // flat scenes need ~0.4
 // the words the pending tile runs' checks read
 static int tile_alloc_words(rb_world *w) {
     if (w->tile_gen) return RB_OK;
-    HIPCHK(hipMalloc((void **)&w->tile_gen, 2 * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&w->tile_why, sizeof(int32_t)));
-    HIPCHK(hipMalloc((void **)&w->tile_commits, sizeof(unsigned long long)));
+    WCHK(w->tile_gen.alloc(2 * sizeof(uint32_t)));
+    WCHK(w->tile_why.alloc(sizeof(int32_t)));
+    WCHK(w->tile_commits.alloc(sizeof(unsigned long long)));
     WCHK(wfill(w, w->tile_why, 0, sizeof(int32_t)));
     WCHK(wfill(w, w->tile_commits, 0, sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void **)&w->tile_host, 4 * sizeof(int64_t), 0));
-    HIPCHK(hipHostMalloc((void **)&w->tile_pub_host, 2 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer((void **)&w->tile_pub_host_d, w->tile_pub_host, 0));
+    WCHK(w->tile_host.alloc(4 * sizeof(int64_t)));
+    WCHK(w->tile_pub_host.alloc(2 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent));
     w->tile_commits_seen = 0;
     return RB_OK;
 }
@@ -126,39 +125,33 @@ static int tile_retire(rb_world *w) {
     if (!w->tile_mem && !w->tile_fill) return RB_OK;
     HIPCHK(hipStreamSynchronize(w->stream));
     drop_graphs(w);
-    if (w->tile_mem) HIPCHK(hipFree(w->tile_mem));
-    if (w->tile_fill) HIPCHK(hipFree(w->tile_fill));
-    w->tile_mem = nullptr;
-    w->tile_fill = nullptr;
-    w->tile_mem_bytes = 0;
+    w->tile_mem.reset();
+    w->tile_fill.reset();
     return RB_OK;
 }
 
 static int tile_alloc(rb_world *w) {
     const size_t need = 2 * tile_bins_bytes(w);
     const size_t slots = (size_t)w->tile_ntx * w->tile_nty;
-    if (w->tile_mem && w->tile_mem_bytes >= need && w->tile_fill) return RB_OK;   // (the fill scratch is sized for the slots too)
+    if (w->tile_mem && w->tile_mem.bytes >= need && w->tile_fill) return RB_OK;   // (the fill scratch is sized for the slots too)
     if (w->tile_mode == -1 && need > TILE_AUTO_MAX_BYTES_PER_BODY * (size_t)w->N) {
         if (int rc = tile_retire(w)) return rc;
         return TILE_DECLINED;
     }
     HIPCHK(hipStreamSynchronize(w->stream));
     drop_graphs(w);                                  // captured bin pointers
-    if (w->tile_mem) { HIPCHK(hipFree(w->tile_mem)); w->tile_mem = nullptr; }
-    if (w->tile_fill) { HIPCHK(hipFree(w->tile_fill)); w->tile_fill = nullptr; }
-    if (hipMalloc(&w->tile_mem, need) != hipSuccess ||
-        hipMalloc((void **)&w->tile_fill, slots * TILE_OFFW * 4) != hipSuccess) {
+    w->tile_mem.reset();
+    w->tile_fill.reset();
+    if (w->tile_mem.alloc(need) || w->tile_fill.alloc(slots * TILE_OFFW * 4)) {
         (void)hipGetLastError();
-        if (w->tile_mem) (void)hipFree(w->tile_mem);
-        w->tile_mem = nullptr;
-        w->tile_mem_bytes = 0;
+        w->tile_mem.reset();
+        w->tile_fill.reset();
         if (w->tile_mode == -1) {
             if (int rc = tile_retire(w)) return rc;
             return TILE_DECLINED;
         }
         return fail(RB_ENOMEM, "tile bins: hipMalloc of %zu bytes failed", need);
     }
-    w->tile_mem_bytes = need;
     return tile_alloc_words(w);
 }
 
@@ -275,15 +268,15 @@ int tile_finish(rb_world *w) {
     if (w->err_pub && w->tile_pub) {
         // the last tile graph published the three words (publish_err_kernel)
         HIPCHK(hipStreamSynchronize(w->stream));
-        err = __atomic_load_n(w->err_host, __ATOMIC_ACQUIRE);
-        why = (int32_t)__atomic_load_n(w->tile_pub_host, __ATOMIC_ACQUIRE);
+        err = __atomic_load_n(w->err_host.get(), __ATOMIC_ACQUIRE);
+        why = (int32_t)__atomic_load_n(w->tile_pub_host.get(), __ATOMIC_ACQUIRE);
         commits = (unsigned long long)__atomic_load_n(w->tile_pub_host + 1, __ATOMIC_ACQUIRE);
     } else {
         HIPCHK(hipMemcpyAsync(w->tile_host, w->err, sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(hipMemcpyAsync(w->tile_host + 1, w->tile_why, sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(hipMemcpyAsync(w->tile_host + 2, w->tile_commits, sizeof(unsigned long long), hipMemcpyDeviceToHost, w->stream));
         HIPCHK(hipStreamSynchronize(w->stream));
-        err = (int32_t)reinterpret_cast<int32_t *>(w->tile_host)[0];
+        err = (int32_t)reinterpret_cast<int32_t *>(w->tile_host.get())[0];
         why = (int32_t)reinterpret_cast<int32_t *>(w->tile_host + 1)[0];
         commits = (unsigned long long)w->tile_host[2];
     }

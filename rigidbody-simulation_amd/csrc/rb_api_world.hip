@@ -9,12 +9,6 @@ using namespace rb::host;
 
 namespace {
 
-int64_t next_pow2(int64_t v) {
-    int64_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 double bound_of(const rb_scene_desc *d, int64_t b) {
     const double *s = d->size + 3 * b;
     return d->kind[b] == RB_BODY_SPHERE ? s[0] : sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
@@ -58,7 +52,7 @@ int upload_consts(rb_world *w, const rb_scene_desc *d, std::vector<double> &boun
         if (types.size() <= (size_t)TILE_TYPES) {
             for (size_t t = 0; t < types.size(); ++t)
                 for (int k = 0; k < 4; ++k) w->tile_type_val[t][k] = (double)types[t][k];
-            HIPCHK(hipMalloc((void **)&w->tile_type_of, (size_t)w->N));
+            WCHK(w->tile_type_of.alloc((size_t)w->N));
             WCHK(wput(w, w->tile_type_of, type_of.data(), (size_t)w->N));
             w->tile_ntypes = (int32_t)types.size();
         }
@@ -69,35 +63,21 @@ int upload_consts(rb_world *w, const rb_scene_desc *d, std::vector<double> &boun
     return RB_OK;
 }
 
+// Teardown: the graphs that captured the buffers, the communicator and the
+// peers' mappings, the events; then every buffer, by its owner's destructor,
+// with the world's device current; the two streams last
 void free_world(rb_world *w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
     drop_graphs(w);
     shard_release(w);
     for (auto &pr : w->tev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    if (w->opt_save) (void)hipFree(w->opt_save);
-    void *tbufs[] = {w->tile_mem, w->tile_fill, w->tile_gen, w->tile_why, w->tile_commits, w->tile_type_of};
-    for (void *b : tbufs)
-        if (b) (void)hipFree(b);
-    if (w->tile_host) (void)hipHostFree(w->tile_host);
-    if (w->tile_pub_host) (void)hipHostFree(w->tile_pub_host);
-    if (w->defer_host) (void)hipHostFree(w->defer_host);
-    if (w->io_q_h) (void)hipHostFree(w->io_q_h);
-    if (w->io_v_h) (void)hipHostFree(w->io_v_h);
-    if (w->io_q_d) (void)hipFree(w->io_q_d);
-    if (w->io_v_d) (void)hipFree(w->io_v_d);
     for (hipEvent_t &e : w->io_ev)
         if (e) (void)hipEventDestroy(e);
-    void *bufs[] = {w->snap[0], w->snap[1], w->qsnap[0], w->qsnap[1], w->defer_q, w->defer_cnt, w->state, w->consts, w->kind, w->xfrc, w->lead_blk, w->ep_mem,
-                    w->ids[0], w->ids[1], w->spill[0], w->spill[1], w->pos[0], w->pos[1], w->plist, w->plist_cnt, w->vel[0], w->vel[1], w->err, w->rec_count, w->rec_partner, w->rec_kind,
-                    w->rec_dist, w->cq_line, w->cq_spill, w->cq_words, w->cq_stage};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (w->err_host) (void)hipHostFree(w->err_host);
-    if (w->cq_stage_h) (void)hipHostFree(w->cq_stage_h);
-    if (w->own_stream) (void)hipStreamDestroy(w->own_stream);
-    if (w->cap_stream) (void)hipStreamDestroy(w->cap_stream);
+    const hipStream_t own_stream = w->own_stream, cap_stream = w->cap_stream;
     delete w;
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    if (cap_stream) (void)hipStreamDestroy(cap_stream);
 }
 
 }  // namespace
@@ -128,188 +108,56 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RB_ENODEV, "no HIP device available");
     if (d->device < 0 || d->device >= ndev) return fail(RB_ENODEV, "device %d out of range (have %d)", d->device, ndev);
 
+    int64_t n_spheres = 0;
+    for (int64_t b = 0; b < d->n_bodies; ++b) n_spheres += d->kind[b] == RB_BODY_SPHERE;
+    const WorldCounts sc{d->n_bodies, d->world_size, d->rank, n_spheres != d->n_bodies, n_spheres, d->dtype == RB_F64 ? 8 : 4,
+                         d->max_partners, d->n_planes};
+    const WorldPlan plan = world_plan(sc, WorldSwitches::from_environ());
+
     rb_world *w = new rb_world();
     w->dtype = d->dtype;
-    w->esz = d->dtype == RB_F64 ? 8 : 4;
+    w->esz = sc.esz;
     w->device = d->device;
-    w->N = d->n_bodies;
-    w->P = d->world_size;
-    w->rank = d->rank;
-    w->S = (w->N + w->P - 1) / w->P;
-    w->Npad = w->S * w->P;
-    w->lo = w->S * w->rank;
-    const int64_t hi = w->lo + w->S < w->N ? w->lo + w->S : w->N;
-    w->n_local = (int32_t)(hi > w->lo ? hi - w->lo : 0);
+    w->N = sc.N;
+    w->P = sc.P;
+    w->rank = sc.rank;
     w->n_planes = d->n_planes;
     for (int k = 0; k < d->n_planes; ++k)
         for (int j = 0; j < 6; ++j) w->planes[k][j] = d->planes[6 * k + j];
     for (int j = 0; j < 3; ++j) w->g[j] = d->gravity[j];
     w->oriented = d->normal_convention == RB_NORMAL_ORIENTED;
-    w->maxp = maxp;
-    bool any_box = false;
-    for (int64_t b = 0; b < d->n_bodies && !any_box; ++b) any_box = d->kind[b] != RB_BODY_SPHERE;
-    // box-capable kernels (sharded worlds exchange the boxes' orientations)
-    w->boxes = any_box;
-    // records per body: 4 per plane, 1 per sphere partner, up to 4 per
-    // partner in scenes with boxes (oracle/rb_oracle_impl.h contact_stride)
-    w->maxrec = 4 * w->n_planes + (any_box ? 4 : 1) * w->maxp;
-    // worlds with boxes: the cooperative form only up to 4,608 owned bodies
-    // (cubes on the incline, per step, helper / plain cooperative / wide:
-    // 4,096 8.6 / 10.7 / 11.7 us, 5,184 10.4 / 12.4 / 10.2, 9,216 12.9 /
-    // 15.7 / 10.2, 16,384 14.7 (plain) / 12.2; scripts/form_ab.py)
-    if (any_box) w->coop_max = 4608;
-    // worlds with boxes keep the helper wave without a share of the search
-    // (C5, 16,384 cubes: about 20 % slower per step with it;
-    // profiles/help_search/shapes_ab.log)
-    if (any_box) w->help_search = false;
-    if (const char *ev = getenv("RBHIP_COOP_MAX_BODIES")) w->coop_max = atoll(ev);
-    if (const char *ev = getenv("RBHIP_WIDE_MAX_BODIES")) w->wide_max = atoll(ev);
-    if (const char *ev = getenv("RBHIP_HELP_MAX_BODIES")) w->help_max = atoll(ev);
-    if (const char *ev = getenv("RBHIP_WIDE_HELP")) w->wide_help = atoi(ev) != 0;
-    if (const char *ev = getenv("RBHIP_HELP_SEARCH")) w->help_search = atoi(ev) != 0;
-    // the cell-ordered tile form (rb_tiles.hip): RBHIP_TILE = 0 off, 1 every
-    // eligible world, -1 auto, the default (eligible worlds of >=
-    // RBHIP_TILE_MIN_BODIES bodies, until their first roll-back): it measures
-    // slower than the hashed forms up to 65,536 flat spheres (C3) and faster
-    // from 73,984 up
-    if (const char *ev = getenv("RBHIP_TILE")) w->tile_mode = atoi(ev) < 0 ? -1 : atoi(ev) ? 1 : 0;
+    static_cast<WorldPlan &>(*w) = plan;
     w->tile_mode_init = w->tile_mode;
-    if (const char *ev = getenv("RBHIP_TILE_MIN_BODIES")) w->tile_min_bodies = atoll(ev);
-    if (const char *ev = getenv("RBHIP_BOX_OPTIMISTIC")) w->box_opt = atoi(ev) != 0;
-    if (const char *ev = getenv("RBHIP_DIAG_OVERFLOW")) w->diag_overflow = atoi(ev);
-    if (const char *ev = getenv("RBHIP_TABLE_EPOCH")) w->epoch_max = std::max(1, std::min(EPOCH_MAX, atoi(ev)));
-    // rb_query_contacts: the bound of its staging buffer
-    if (const char *ev = getenv("RBHIP_CONTACT_STAGE_BYTES"))
-        if (atoll(ev) > 0) w->cq_limit = (size_t)atoll(ev);
-    // buckets: cooperative worlds (a hash per cell; they also keep a slot
-    // snapshot line per bucket) 16 per body; the one-lane and wide forms
-    // (linear cell groups, below) 32 per body, so the groups' period spans
-    // the scene (C3: 2^21 buckets, 205 m x 102 m x 12.8 m; as fast as 2^23,
-    // 16 per body 20 % slower: the period then folds the scene onto itself).
-    // At most 2^26 buckets (8 GB of lines per table).
-    const bool coop_world = w->n_local <= w->coop_max;
-    int64_t want = coop_world ? 16 * w->N : 32 * w->N;
-    if (const char *ev = getenv("RBHIP_HASH_FACTOR"))
-        if (atoll(ev) > 0) want = atoll(ev) * w->N;
-    if (want < 4096) want = 4096;
-    // memory cap over both tables (lines, plus slot snapshots in cooperative
-    // worlds): RBHIP_HASH_MAX_BYTES, default 8 GiB (1M bodies keep 32 buckets
-    // per body, 4M bodies get 8)
-    const int64_t per_bucket = 2 * (int64_t)(sizeof(uint32_t) * LINE_WORDS + (coop_world ? w->esz * 4 * LINE_WORDS : 0));
-    int64_t cap_bytes = int64_t(8) << 30;
-    if (const char *ev = getenv("RBHIP_HASH_MAX_BYTES"))
-        if (atoll(ev) > 0) cap_bytes = atoll(ev);
-    int64_t hmax = 4096;
-    while (hmax * 2 * per_bucket <= cap_bytes && hmax < (int64_t(1) << 26)) hmax *= 2;
-    w->H = next_pow2(want) < hmax ? next_pow2(want) : hmax;
-    w->hmax = hmax;
-    // The one-lane and wide forms group cells 8x8x4, the buckets of a group
-    // contiguous (32 KB of lines), and lay the groups out linearly, periodic
-    // in 2^lx x 2^ly x 2^lz groups (below): against a hash per cell measured
-    // 6 % faster at 65k bodies (flat), 5 % (incline), 12 % at 1M; hashed
-    // groups were bimodal (a group collision doubles the bodies of every
-    // bucket in both groups and sends waves through the wide form's extra
-    // round trip for buckets of 7+ ids).  Those kernels compute
-    // the linear layout directly (rb_grid.hpp LAYOUT_LINEAR), so their worlds
-    // always use it.  The cooperative form keeps a hash per cell.
-    // RBHIP_HASH_GROUP=bx:by:bz sets the group shape (2^bx x 2^by x 2^bz
-    // cells); in cooperative worlds bx:by:bz hashes the groups and
-    // bx:by:bz:l lays them out linearly.
-    int gshape = coop_world ? 0 : 0x233;
-    bool linear = !coop_world;
-    if (const char *ev = getenv("RBHIP_HASH_GROUP")) {
-        int bx = 0, by = 0, bz = 0;
-        char mode = 'h';
-        if (sscanf(ev, "%d:%d:%d:%c", &bx, &by, &bz, &mode) >= 3 && bx >= 0 && by >= 0 && bz >= 0 && bx + by + bz <= 12)
-            gshape = bx | (by << 4) | (bz << 8);
-        if (coop_world) linear = mode == 'l';
-    }
-    auto gbits = [](int g) { return (g & 15) + ((g >> 4) & 15) + ((g >> 8) & 15); };
-    // a table too small for the groups: smaller groups (linear), none (hashed)
-    while (gshape && (int64_t(1) << gbits(gshape)) > w->H / 4) {
-        if (!linear) { gshape = 0; break; }
-        for (int sh = 8; sh >= 0; sh -= 4)
-            if ((gshape >> sh) & 15) { gshape -= 1 << sh; break; }
-    }
-    w->group = gshape;
-    if (linear) {
-        // the group slots split into a period of 2^lx x 2^ly x 2^lz groups (z: at most 8)
-        int lg = 0;
-        while ((int64_t(1) << (lg + 1)) <= w->H) ++lg;
-        lg -= gbits(gshape);
-        const int lz = lg / 3 < 3 ? lg / 3 : 3, lx = (lg - lz + 1) / 2, ly = lg - lz - lx;
-        int l[3] = {lx, ly, lz};
-        // diagnostic: RBHIP_HASH_PERIOD=lx:ly:lz sets the creation-time split
-        // (at most the table's group bits; with RBHIP_FIT_PERIOD=0 it stays).
-        // A zero on an axis whose groups are one cell thick makes a body's
-        // two cells along that axis one bucket (tests of the visit-once rule)
-        if (const char *ev = getenv("RBHIP_HASH_PERIOD")) {
-            int a = 0, b = 0, c = 0;
-            if (sscanf(ev, "%d:%d:%d", &a, &b, &c) == 3 && a >= 0 && b >= 0 && c >= 0 && a <= 15 && b <= 15 && c <= 15 &&
-                a + b + c <= lg) { l[0] = a; l[1] = b; l[2] = c; }
-        }
-        w->group |= (l[0] << 12) | (l[1] << 16) | (l[2] << 20) | (1 << 24);
-    }
-    // heads per 128-byte line (rb_internal.hpp Table): 4 in wide-form worlds
-    // (C3 17.4 -> 16.4 us), 2 in one-lane worlds (1M 0.237 -> 0.225 ms; 4
-    // there cost 10 % at 262k), 1 in cooperative worlds (no gain measured).
-    // The cooperative and wide kernels assume theirs at compile time;
-    // RBHIP_HEADS_PER_LINE = 1, 2 or 4 sets the one-lane worlds'.
-    const bool wide_world = !coop_world && w->n_local <= w->wide_max;
-    int rl = coop_world ? 0 : wide_world ? 2 : 1;
-    if (const char *ev = getenv("RBHIP_HEADS_PER_LINE"))
-        if (!coop_world && !wide_world) {
-            const int r = atoi(ev);
-            if (r == 1 || r == 2 || r == 4) rl = r == 1 ? 0 : r == 2 ? 1 : 2;
-        }
-    w->group |= rl << 25;
-    int64_t nsph = 0;
-    for (int64_t b = 0; b < w->N; ++b) nsph += d->kind[b] == RB_BODY_SPHERE;
-    // algorithmic bytes per body-step: 13 state reals read + 13
-    // written + constants (m, I[3], r | h[3])
-    w->bytes_per_body_step = (int64_t)w->esz * (26 + 4) + (int64_t)w->esz * ((nsph * 1 + (w->N - nsph) * 3) / w->N);
 
     auto bail = [&](int rc) { free_world(w); return rc; };
     if (hipSetDevice(w->device) != hipSuccess) return bail(fail(RB_ENODEV, "hipSetDevice(%d) failed", w->device));
-#define ALLOC(ptr, bytes)                                                                        \
-    do {                                                                                         \
-        if (hipMalloc((void **)&(ptr), (bytes)) != hipSuccess)                                   \
-            return bail(fail(RB_ENOMEM, "hipMalloc(%lld) failed", (long long)(bytes)));          \
-    } while (0)
-    for (int k = 0; k < 2; ++k) ALLOC(w->snap[k], (size_t)w->esz * 4 * w->Npad);
+    // (after a failure nothing more is allocated)
+    int arc = RB_OK;
+    auto alloc = [&](DevMem &b, size_t bytes) { if (!arc) arc = b.alloc(bytes); };
+    for (int k = 0; k < 2; ++k) alloc(w->snap[k], snap_bytes(w));
     if (w->boxes) {
-        for (int k = 0; k < 2; ++k) ALLOC(w->qsnap[k], (size_t)w->esz * 4 * w->Npad);
-        ALLOC(w->defer_q, sizeof(int32_t) * (w->S > 0 ? w->S : 1));
-        ALLOC(w->defer_cnt, sizeof(int32_t) * 2);
+        for (int k = 0; k < 2; ++k) alloc(w->qsnap[k], snap_bytes(w));
+        alloc(w->defer_q, sizeof(int32_t) * (w->S > 0 ? w->S : 1));
+        alloc(w->defer_cnt, sizeof(int32_t) * 2);
     }
-    ALLOC(w->state, (size_t)w->esz * 13 * w->S);
-    ALLOC(w->consts, (size_t)w->esz * 8 * w->Npad);
-    ALLOC(w->kind, sizeof(int32_t) * w->Npad);
-    ALLOC(w->lead_blk, sizeof(uint32_t) * LEAD_WORDS);   // (hipMalloc: aligned to 16 bytes and more)
-    w->gen = w->lead_blk + LEAD_GEN;
-    ALLOC(w->ep_mem, sizeof(uint32_t) * 8);
-    // Opt-in (RBHIP_SPLIT=1): large scenes step in two kernels (search,
-    // update) joined by a partner list; bit-exact with the oracle on the
-    // device (tests/test_gpu_parity.py ragged-scene test) but no faster
-    // (DESIGN §5), so the default is the fused one-kernel step.
-    const char *split_env = getenv("RBHIP_SPLIT");
-    const bool coop = w->n_local <= w->coop_max;
-    const bool split = !coop && !w->boxes && split_env && atoi(split_env) == 1;
-    if (split) {
-        ALLOC(w->plist, sizeof(int32_t) * (w->maxp <= 16 ? 16 : 32) * w->S);
-        ALLOC(w->plist_cnt, sizeof(int32_t) * w->S);
+    alloc(w->state, state_bytes(w));
+    alloc(w->consts, consts_bytes(w));
+    alloc(w->kind, sizeof(int32_t) * w->Npad);
+    alloc(w->lead_blk, sizeof(uint32_t) * LEAD_WORDS);   // (hipMalloc: aligned to 16 bytes and more)
+    alloc(w->ep_mem, sizeof(uint32_t) * 8);
+    if (w->split) {
+        alloc(w->plist, sizeof(int32_t) * (w->maxp <= 16 ? 16 : 32) * w->S);
+        alloc(w->plist_cnt, sizeof(int32_t) * w->S);
     }
     for (int k = 0; k < 2; ++k) {
-        ALLOC(w->ids[k], sizeof(uint32_t) * LINE_WORDS * w->H);
-        ALLOC(w->spill[k], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES);
-        // slot snapshots feed the cooperative search only
-        if (needs_slot_snapshots(coop, split)) ALLOC(w->pos[k], (size_t)w->esz * 4 * LINE_WORDS * w->H);
+        alloc(w->ids[k], line_bytes(w->H));
+        alloc(w->spill[k], spill_bytes);
+        if (w->slot_snapshots) alloc(w->pos[k], slot_snapshot_bytes(w));
     }
-    ALLOC(w->err, sizeof(int32_t));
-#undef ALLOC
-    if (hipHostMalloc((void **)&w->err_host, sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&w->err_host_d, w->err_host, 0) != hipSuccess)
-        return bail(fail(RB_ENOMEM, "hipHostMalloc failed"));
+    alloc(w->err, sizeof(int32_t));
+    if (!arc) arc = w->err_host.alloc(sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent);
+    if (arc) return bail(arc);
+    w->gen = w->lead_blk + LEAD_GEN;
     *w->err_host = 0;
     if (hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&w->cap_stream, hipStreamNonBlocking) != hipSuccess)
@@ -317,12 +165,9 @@ int rb_world_create(rb_world **out, const rb_scene_desc *d) {
     w->stream = w->own_stream;
     {
         const std::pair<void *, size_t> zero[] = {
-            {w->snap[0], (size_t)w->esz * 4 * w->Npad}, {w->snap[1], (size_t)w->esz * 4 * w->Npad},
-            {w->state, (size_t)w->esz * 13 * w->S},
+            {w->snap[0], snap_bytes(w)}, {w->snap[1], snap_bytes(w)}, {w->state, state_bytes(w)},
             // bucket headers of generation 0: every table's generation is >= 2
-            {w->ids[0], sizeof(uint32_t) * LINE_WORDS * w->H}, {w->ids[1], sizeof(uint32_t) * LINE_WORDS * w->H},
-            {w->spill[0], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES},
-            {w->spill[1], sizeof(uint32_t) * SPILL_LINE_WORDS * SPILL_LINES},
+            {w->ids[0], line_bytes(w->H)}, {w->ids[1], line_bytes(w->H)}, {w->spill[0], spill_bytes}, {w->spill[1], spill_bytes},
             {w->lead_blk, sizeof(uint32_t) * LEAD_WORDS}, {w->ep_mem, sizeof(uint32_t) * 8}, {w->err, sizeof(int32_t)}, {w->defer_cnt, sizeof(int32_t) * 2}};
         for (const auto &z : zero)
             if (z.first && hipMemsetAsync(z.first, 0, z.second, w->stream) != hipSuccess)
@@ -364,10 +209,10 @@ int rb_set_xfrc(rb_world *w, const double *xf) {
     if (int rc = finish_pending(w)) return rc;
     if (!xf) {
         // (graphs capture whether a step reads applied forces)
-        if (w->xfrc) { drop_graphs(w); HIPCHK(hipStreamSynchronize(w->stream)); HIPCHK(hipFree(w->xfrc)); w->xfrc = nullptr; }
+        if (w->xfrc) { drop_graphs(w); HIPCHK(hipStreamSynchronize(w->stream)); w->xfrc.reset(); }
         return RB_OK;
     }
-    if (!w->xfrc) { drop_graphs(w); HIPCHK(hipMalloc(&w->xfrc, (size_t)w->esz * 6 * w->S)); }
+    if (!w->xfrc) { drop_graphs(w); WCHK(w->xfrc.alloc((size_t)w->esz * 6 * w->S)); }
     HIPCHK(hipStreamSynchronize(w->stream));             // (steps in flight read the old forces)
     return by_real(w->dtype, [&](auto t) {
         using T = decltype(t);
@@ -384,11 +229,11 @@ int rb_record_contacts(rb_world *w, int enable) {
     HIPCHK(hipSetDevice(w->device));
     if (int rc = finish_pending(w)) return rc;
     if (enable && !w->rec_count) {
-        const size_t slots = (size_t)w->maxrec * (w->S > 0 ? w->S : 1);
-        HIPCHK(hipMalloc((void **)&w->rec_count, sizeof(int32_t) * w->S));
-        HIPCHK(hipMalloc((void **)&w->rec_partner, sizeof(int32_t) * slots));
-        HIPCHK(hipMalloc((void **)&w->rec_kind, sizeof(int32_t) * slots));
-        HIPCHK(hipMalloc(&w->rec_dist, (size_t)w->esz * slots));
+        const size_t slots = record_slots(w);
+        WCHK(w->rec_count.alloc(sizeof(int32_t) * w->S));
+        WCHK(w->rec_partner.alloc(sizeof(int32_t) * slots));
+        WCHK(w->rec_kind.alloc(sizeof(int32_t) * slots));
+        WCHK(w->rec_dist.alloc((size_t)w->esz * slots));
         WCHK(wfill(w, w->rec_count, 0, sizeof(int32_t) * w->S));
     }
     if (w->record != (enable != 0)) drop_graphs(w);
@@ -403,7 +248,7 @@ int rb_get_contacts(rb_world *w, int32_t *counts, int32_t *partner, int32_t *kin
     if (!w->rec_count) return fail(RB_EINVAL, "contact recording was never enabled");
     HIPCHK(hipSetDevice(w->device));
     if (int rc = finish_pending(w)) return rc;
-    const size_t slots = (size_t)w->maxrec * w->S;
+    const size_t slots = record_slots(w);
     std::vector<int32_t> c((size_t)w->S), pa(slots), ki(slots);
     std::vector<double> di(slots);
     HIPCHK(hipMemcpyAsync(c.data(), w->rec_count, sizeof(int32_t) * w->S, hipMemcpyDeviceToHost, w->stream));
@@ -454,7 +299,7 @@ int rb_set_contact_law(rb_world *w, int32_t law, double tol) {
     if (law == RB_LAW_BALLS && !w->vel[0]) {
         const size_t bytes = (size_t)w->esz * 8 * w->Npad;
         for (int k = 0; k < 2; ++k) {
-            if (hipMalloc(&w->vel[k], bytes) != hipSuccess) return fail(RB_ENOMEM, "hipMalloc(%zu) failed", bytes);
+            WCHK(w->vel[k].alloc(bytes));
             WCHK(wfill(w, w->vel[k], 0, bytes));
         }
     }
@@ -464,7 +309,7 @@ int rb_set_contact_law(rb_world *w, int32_t law, double tol) {
         // other way, the true positions from the snapshot
         const bool to_snap = law == RB_LAW_MUJOCO;
         const size_t esz = (size_t)w->esz;
-        std::vector<char> st(esz * 13 * w->S), sn(esz * 4 * w->Npad);
+        std::vector<char> st(state_bytes(w)), sn(snap_bytes(w));
         HIPCHK(hipMemcpyAsync(st.data(), w->state, st.size(), hipMemcpyDeviceToHost, w->stream));
         WCHK(wget(w, sn.data(), w->snap[w->sp()], sn.size()));
         for (int64_t l = 0; l < w->n_local; ++l)

@@ -87,7 +87,7 @@ int rb_set_xfrc_dev(rb_world *w, const void *xfrc, int32_t io_dtype) {
         // (graphs capture whether a step reads applied forces: rb_set_xfrc)
         HIPCHK(hipStreamSynchronize(w->stream));
         drop_graphs(w);
-        HIPCHK(hipMalloc(&w->xfrc, (size_t)w->esz * 6 * w->S));
+        WCHK(w->xfrc.alloc((size_t)w->esz * 6 * w->S));
         WCHK(wfill(w, w->xfrc, 0, (size_t)w->esz * 6 * w->S));
     }
     // steps in flight read the old forces: they precede the kernel on the stream

@@ -20,106 +20,79 @@
 
 #include "../../include/rbhip.h"
 #include "rb_internal.hpp"
+#include "rb_owned.hpp"
+#include "rb_worldplan.hpp"
 
 using namespace rb;
+using rb::host::DevBuf;
+using rb::host::HostBuf;
 
-struct rb_world {
+// A world starts as its plan (rb_worldplan.hpp WorldPlan: the shard, the form
+// thresholds, the table and its layout word, the switches).  Growth and refits
+// move maxp, maxrec, H and group; the tile form's retirement, tile_mode
+struct rb_world : WorldPlan {
     int dtype = RB_F64, esz = 8, device = 0;
     hipStream_t stream = nullptr, own_stream = nullptr, cap_stream = nullptr;
-    int64_t N = 0, S = 0, Npad = 0, lo = 0;
-    int32_t n_local = 0, P = 1, rank = 0;
-    int32_t n_planes = 0, oriented = 1, maxp = 16, maxrec = 0;
-    // owned bodies up to which the cooperative search is used: above it
-    // the wide form (with its helper wave) is faster (19,600: 14.4 vs 12.1
-    // us; 16,384: 11.1 vs 11.3, 12,100: 10.4 vs 11.5 the other way;
-    // profiles/r03/wide_help/ab_thresh_flat.txt)
-    int64_t coop_max = 16384;
-    // above coop_max, up to which the wide one-lane form is used; with its
-    // helper wave it is at least as fast as the one-lane form at every size
-    // measured (131k / 262k equal, 524k 0.116 -> 0.102 ms, 1M 0.236 ->
-    // 0.216, 4M 0.876 -> 0.841; profiles/r03/wide_help/ab_large2.txt), so
-    // the one-lane form only runs on request (RBHIP_WIDE_MAX_BODIES)
-    int64_t wide_max = INT64_MAX;
-    // owned bodies up to which the cooperative form runs with a helper wave
-    // per workgroup (inv(I_w), gravity and plane contacts off the body
-    // lanes' chain): 4k 8.1 -> 7.4 us, 8k 9.6 -> 8.6; 16k 11.0 -> 11.9 the
-    // other way (its waves then share SIMDs)
-    int64_t help_max = 12288;
-    // the wide form with a helper wave per workgroup (inv(I_w), gravity,
-    // plane contacts and the state / constant loads off the body wave;
-    // A/B steps 261-460, profiles/r03/wide_help_ab.txt): 32k 13.6 -> 12.9
-    // us, C3 16.8 -> 16.1, C4 15.4 -> 14.9, C5 (16,384 cubes) 12.1 -> 9.6
-    bool wide_help = true;
-    // that form with the contact search shared between its two waves: the
-    // helper lane of a body searches four of its eight buckets (rb_grid.hpp
-    // search_half_wide; RBHIP_HELP_SEARCH)
-    bool help_search = true;
+    int64_t N = 0;
+    int32_t P = 1, rank = 0;
+    int32_t n_planes = 0, oriented = 1;
     double planes[RB_MAX_PLANES][6] = {};
     double g[3] = {};
     double inv_cs = 1.0;
     double rmax = 0.0;             // largest bounding radius
     bool all_spheres = true;
-    bool boxes = false;            // box-capable step kernels (any box body; sharded worlds exchange orientations)
     // contact law (rb_set_contact_law)
     int32_t law = RB_LAW_MUJOCO;
     double tol = 0.01;
     double prm_dt = 0, prm_e = 0, prm_mu = 0;   // the ground phase held in the snapshots (two-ball law)
-    int64_t H = 4096;
-    int64_t hmax = 4096;           // the table's growth limit (RBHIP_HASH_MAX_BYTES)
-    int32_t group = 0;             // Grid::super: bucket grouping shape (x | y << 4 | z << 8 bits)
     bool fit_valid = false;        // fit_period: the group box (and layout) the last fit was made for
     int64_t fit_key[7] = {};
-    int64_t bytes_per_body_step = 0;
     std::vector<double> bound;     // host copy of every body's bounding radius (rb_set_state's snapshot rows)
-    // device memory
-    void *snap[2] = {};        // [Npad] Snap<T>: (x, y, z, bound radius), ping-pong
-    void *qsnap[2] = {};       // boxes: [Npad][4] step-start orientations, ping-pong with snap
-    int32_t *defer_q = nullptr;    // boxes: [S] bodies the step kernel defers to the box kernel
-    int32_t *defer_cnt = nullptr;  // boxes: [2] queue lengths by step parity
+    // device memory (rb_owned.hpp: every buffer below is released with the world)
+    DevBuf<void> snap[2];       // [Npad] Snap<T>: (x, y, z, bound radius), ping-pong
+    DevBuf<void> qsnap[2];      // boxes: [Npad][4] step-start orientations, ping-pong with snap
+    DevBuf<int32_t> defer_q;      // boxes: [S] bodies the step kernel defers to the box kernel
+    DevBuf<int32_t> defer_cnt;    // boxes: [2] queue lengths by step parity
     // box worlds, one rank: chunks of steps replay optimistically WITHOUT the
     // box kernel (an idle one still costs a kernel boundary per step); the
     // step kernels then only count deferrals, and a chunk that deferred any
     // body is rolled back to its start and replayed with the box kernel
-    bool box_opt = true;           // RBHIP_BOX_OPTIMISTIC=0: always launch the box kernel
+    // (if box_opt, the plan's)
     bool box_kernel_on = true;     // launch_one: the box kernel follows the step kernel
     int32_t box_backoff = 0;       // chunks to run with the box kernel after a rollback (doubles)
     int32_t box_skip = 0;          // of which left
-    void *opt_save = nullptr;      // chunk-start copy: state rows, snapshot, orientations, error word
-    int32_t *defer_host = nullptr; // pinned [2]
+    DevBuf<void> opt_save;        // chunk-start copy: state rows, snapshot, orientations, error word
+    HostBuf<int32_t> defer_host;   // pinned [2]
     int64_t box_stats[2] = {};     // optimistic chunks, rollbacks
     bool sync_call = false;        // inside rb_step (synchronous): long chunks are guarded
     int64_t refits = 0;            // layout refits after a bucket overflow (rolled back, replayed)
     int64_t table_grows = 0;       // of which with the table doubled
     int64_t partner_grows = 0;     // max_partners raised 16 -> 32 after a partner overflow
-    int32_t diag_overflow = 0;     // RBHIP_DIAG_OVERFLOW=n (tests): the next n guarded chunk checks
-                                   // report a bucket overflow (the roll-back / refit / growth path)
-    void *state = nullptr;     // 13 x S  (qw qx qy qz vx vy vz wx wy wz px py pz)
-    void *vel[2] = {};         // two-ball law: [Npad] Vel<T>, ping-pong with the snapshots
-    void *consts = nullptr;    // 8 x Npad (mass ix iy iz sx sy sz bound)
-    int32_t *kind = nullptr;   // Npad
-    void *xfrc = nullptr;      // 6 x S or null
-    uint32_t *ids[2] = {};     // [H][LINE_WORDS] bucket blocks (rb_internal.hpp Table; alternate with the snapshots)
-    uint32_t *spill[2] = {};   // [SPILL_LINES x SPILL_LINE_WORDS] ids past full buckets, per table
-    void *pos[2] = {};         // [H][LINE_WORDS] Snap<T> bucket slot snapshots
+    DevBuf<void> state;       // 13 x S  (qw qx qy qz vx vy vz wx wy wz px py pz)
+    DevBuf<void> vel[2];        // two-ball law: [Npad] Vel<T>, ping-pong with the snapshots
+    DevBuf<void> consts;      // 8 x Npad (mass ix iy iz sx sy sz bound)
+    DevBuf<int32_t> kind;     // Npad
+    DevBuf<void> xfrc;        // 6 x S or null
+    DevBuf<uint32_t> ids[2];    // [H][LINE_WORDS] bucket blocks (rb_internal.hpp Table; alternate with the snapshots)
+    DevBuf<uint32_t> spill[2];  // [SPILL_LINES x SPILL_LINE_WORDS] ids past full buckets, per table
+    DevBuf<void> pos[2];        // [H][LINE_WORDS] Snap<T> bucket slot snapshots
     // the step kernels' lead block (rb_internal.hpp LEAD_WORDS), one allocation:
     // generations [2] and epoch control words [2] by step parity.  prime()
     // writes the current parity's words; the step kernels' block 0 the other's
-    uint32_t *lead_blk = nullptr;
+    DevBuf<uint32_t> lead_blk;
     uint32_t *gen = nullptr;   // [2] generation of the table of each step parity (rb_internal.hpp Table): lead_blk + LEAD_GEN
     uint32_t gen_off = 1;      // an upper bound of step c's generation: gen_off + c (host bookkeeping; only
                                // grows; append steps keep their table's generation, so the device's lag it)
     // append epochs (rb_internal.hpp Epoch): the control words [2] by step
     // parity are lead_blk + LEAD_CTRL; ep_mem, one allocation — two unused
     // words, crowding flags [2], counters [2] (append steps, rebuild steps)
-    int32_t epoch_max = EPOCH_DEFAULT;   // RBHIP_TABLE_EPOCH; 1: every step rebuilds its next table
-    uint32_t *ep_mem = nullptr;
+    DevBuf<uint32_t> ep_mem;
     uint32_t *ep_ctrl() const { return lead_blk + LEAD_CTRL; }
     bool ep_primed = false;        // the last prime() started an epoch schedule
-    int32_t *plist = nullptr;      // split form: [MAXP][S] sorted partner ids
-    int32_t *plist_cnt = nullptr;  // split form: [S] partner counts
-    int32_t *err = nullptr;
-    int32_t *err_host = nullptr;   // pinned, device-mapped (publish_err_kernel writes it)
-    int32_t *err_host_d = nullptr;
+    DevBuf<int32_t> plist;        // split form: [MAXP][S] sorted partner ids
+    DevBuf<int32_t> plist_cnt;    // split form: [S] partner counts
+    DevBuf<int32_t> err;
+    HostBuf<int32_t> err_host;     // pinned, device-mapped (publish_err_kernel writes it)
     // err_host holds the error word as of all error-writing work enqueued so
     // far: set by a graph launch (every captured graph ends in
     // publish_err_kernel), cleared by every builder of kernel parameters that
@@ -129,21 +102,21 @@ struct rb_world {
     ncclComm_t comm = nullptr;     // rb_shard_comm_init: the in-library exchange
     // peer-to-peer exchange (rb_p2p_connect)
     bool p2p = false;
-    int64_t *flags = nullptr;      // the mailbox (MailLayout, uncached); starts with flags[P]: peer q
+    DevBuf<int64_t> flags;        // the mailbox (MailLayout, uncached); starts with flags[P]: peer q
                                    // writes slot q when its step is done
     bool halo = false;             // rb_p2p_halo: push only the bodies a peer can reach
-    int32_t *bounds = nullptr;     // peer-to-peer: [2][BOUND_COPIES][BOUND_STRIDE] own cell bounds (step parity)
-    int32_t *push_cnt = nullptr;   // halo: [P] bodies pushed to each peer this step
-    int64_t *halo_e = nullptr;     // halo: the epoch the next step kernel's pushes test against
-    int64_t *epoch = nullptr;      // steps taken since connect (advanced by the step kernel)
-    void **peer_snap_dev = nullptr;       // [2][P] device array: each rank's snapshot buffers
-    void **peer_quat_dev = nullptr;       // box worlds: [2][P] each rank's orientation snapshots
-    int64_t **peer_flags_dev = nullptr;   // [P] device array: each rank's flag array
+    DevBuf<int32_t> bounds;       // peer-to-peer: [2][BOUND_COPIES][BOUND_STRIDE] own cell bounds (step parity)
+    DevBuf<int32_t> push_cnt;     // halo: [P] bodies pushed to each peer this step
+    DevBuf<int64_t> halo_e;       // halo: the epoch the next step kernel's pushes test against
+    DevBuf<int64_t> epoch;        // steps taken since connect (advanced by the step kernel)
+    DevBuf<void *> peer_snap_dev;        // [2][P] device array: each rank's snapshot buffers
+    DevBuf<void *> peer_quat_dev;        // box worlds: [2][P] each rank's orientation snapshots
+    DevBuf<int64_t *> peer_flags_dev;  // [P] device array: each rank's flag array
     std::vector<void *> ipc_opened;       // peer mappings to close
     // recording
     bool record = false;
-    int32_t *rec_count = nullptr, *rec_partner = nullptr, *rec_kind = nullptr;
-    void *rec_dist = nullptr;
+    DevBuf<int32_t> rec_count, rec_partner, rec_kind;
+    DevBuf<void> rec_dist;
     // stepping state: step counter c; bucket counts rotate mod 3, snapshots
     // and bucket slots mod 2
     int64_t c = 0;
@@ -159,10 +132,9 @@ struct rb_world {
     // way and transposed by a kernel.  The staging mirrors the device state
     // while mirror_version == state_version (every change of the state bumps
     // it): an rb_set_state with exactly those bytes is then a no-op
-    double *io_q_h = nullptr, *io_v_h = nullptr;   // pinned [N][7], [N][6]
-    double *io_q_hd = nullptr, *io_v_hd = nullptr; // the same pinned rows, device-mapped (rb_get_state's kernel writes them)
+    HostBuf<double> io_q_h, io_v_h;                // pinned [N][7], [N][6], device-mapped (rb_get_state's kernel writes them)
     hipEvent_t io_ev[4] = {};      // rb_get_state (RBHIP_IO_OUT=1): the download in chunks, each copied out as it lands
-    double *io_q_d = nullptr, *io_v_d = nullptr;   // device
+    DevBuf<double> io_q_d, io_v_d;                 // device
     int64_t state_version = 0, mirror_version = -1;
     int64_t io_stats[2] = {};      // rb_set_state calls skipped (unchanged), uploads
     // kernel timing
@@ -180,23 +152,20 @@ struct rb_world {
     // failed run leaves the id-ordered state at the start of the first
     // failed run, which the host replays with the hashed-cell forms
     // (tile_finish) at the next sync point.
-    int tile_mode = -1;            // RBHIP_TILE: 0 off, 1 every eligible world, -1 auto (default: >= tile_min_bodies, off after a roll-back)
     int tile_mode_init = -1;       // the mode at creation (auto: re-armed by an rb_set_state that uploads)
     int32_t tile_ntypes = 0;       // distinct (m, I) of the bodies when <= TILE_TYPES (else 0: no tile form)
     double tile_type_val[TILE_TYPES][4] = {};   // m ix iy iz of each type
-    uint8_t *tile_type_of = nullptr;   // [N]
-    int64_t tile_min_bodies = 65537;    // (the hashed forms win up to C3's 65,536 bodies, the tile form above: DESIGN §4.1)
+    DevBuf<uint8_t> tile_type_of;     // [N]
     int32_t tile_tc = 0, tile_ntx = 0, tile_nty = 0, tile_cap = TILE_THREADS;
     bool tile_fit_valid = false;
     int tile_valid_sp = -1;        // the bins of this parity hold the state at step c (-1: no bins)
-    void *tile_mem = nullptr;      // bins x 2 (column tables, positions, ids, state), far lists x 2
-    size_t tile_mem_bytes = 0;
-    int32_t *tile_fill = nullptr;  // build scratch [slots][TILE_OFFW]
-    uint32_t *tile_gen = nullptr;  // [2] generation of each parity's bins (far-list tags)
-    int32_t *tile_why = nullptr;   // TILE_WHY_* bits raised (device)
-    unsigned long long *tile_commits = nullptr;   // runs committed by the unbin kernel (device)
-    int64_t *tile_host = nullptr;  // pinned: err, why, commits
-    int64_t *tile_pub_host = nullptr, *tile_pub_host_d = nullptr;   // pinned, mapped: why, commits (tile graphs' publish)
+    DevBuf<void> tile_mem;         // bins x 2 (column tables, positions, ids, state), far lists x 2
+    DevBuf<int32_t> tile_fill;    // build scratch [slots][TILE_OFFW]
+    DevBuf<uint32_t> tile_gen;    // [2] generation of each parity's bins (far-list tags)
+    DevBuf<int32_t> tile_why;     // TILE_WHY_* bits raised (device)
+    DevBuf<unsigned long long> tile_commits;  // runs committed by the unbin kernel (device)
+    HostBuf<int64_t> tile_host;   // pinned: err, why, commits
+    HostBuf<int64_t> tile_pub_host;                               // pinned, mapped: why, commits (tile graphs' publish)
     bool tile_pub = false;         // err_pub, and the last graph was a tile run's (tile_pub_host is current)
     unsigned long long tile_commits_seen = 0;
     // a tile run whose check waits for the next sync point
@@ -212,15 +181,16 @@ struct rb_world {
     // word) for the grid of cq_H buckets and line layout cq_layout, and the
     // host form's staging (device, pinned twin; at most cq_limit bytes).
     // Nothing else of the world is written by a query
-    uint32_t *cq_line = nullptr, *cq_spill = nullptr, *cq_words = nullptr;
+    DevBuf<uint32_t> cq_line, cq_spill, cq_words;
     int64_t cq_H = 0;
     int32_t cq_layout = 0;
     uint32_t cq_gen = 0;           // the generation of the last query (0: the table holds zeros)
-    char *cq_stage = nullptr, *cq_stage_h = nullptr;
+    DevBuf<char> cq_stage;
+    HostBuf<char> cq_stage_h;
     size_t cq_stage_bytes = 0;
-    size_t cq_limit = (size_t)256 << 20;   // RBHIP_CONTACT_STAGE_BYTES
 
     int sp() const { return (int)(c % 2); }
+    __attribute__((visibility("hidden"))) ~rb_world() = default;   // (the owners release the buffers: free_world)
 };
 
 // Everything the host units share beyond the world lives in rb::host, hidden:
@@ -288,10 +258,6 @@ inline int wget(rb_world *w, void *dst, const void *src, size_t bytes) {
     return RB_OK;
 }
 
-// A device buffer that only grows: afterwards *buf holds `need` bytes or more.
-// (The capacity is zero while the buffer is being replaced: an error in between
-// leaves an empty buffer, not a dangling one.)
-int grow(void **buf, size_t *cap, size_t need);
 // Every array of a device form that is given: device memory on `device`.
 // owner: "batch" / "world", for the message.  (A refusal leaves no HIP error behind.)
 int dev_ptrs(int device, const char *owner, std::initializer_list<std::pair<const void *, const char *>> arrays);
@@ -301,6 +267,13 @@ inline int64_t count_truncated(const int32_t *counts, size_t bodies, int32_t R) 
     for (size_t k = 0; k < bodies; ++k) t += counts[k] > R;
     return t;
 }
+
+// the byte counts of this world's buffers (rb_worldplan.hpp)
+inline size_t snap_bytes(const rb_world *w) { return rb::snap_bytes(w->esz, w->Npad); }
+inline size_t state_bytes(const rb_world *w) { return rb::state_bytes(w->esz, w->S); }
+inline size_t consts_bytes(const rb_world *w) { return rb::consts_bytes(w->esz, w->Npad); }
+inline size_t slot_snapshot_bytes(const rb_world *w) { return rb::slot_snapshot_bytes(w->esz, w->H); }
+inline size_t record_slots(const rb_world *w) { return rb::record_slots(w->maxrec, w->S); }
 
 template <typename T> T *dp(void *p, int64_t off) { return reinterpret_cast<T *>(p) + off; }
 
@@ -322,9 +295,15 @@ void drop_graphs(rb_world *w);
 int graph_replay(rb_world *w, int64_t K, int variant, double dt, double e, double mu, double thr,
                  const std::function<int(hipStream_t, int64_t)> &seq);
 int gen_guard(rb_world *w, int64_t nsteps);
+int enqueue_steps(rb_world *w, int64_t nsteps, double dt, double e, double mu, double thr, bool sharded = false);
+
+// ---- rb_api_guard.hip --------------------------------------------------------
+constexpr int64_t GUARD_MIN_STEPS = 64;   // shorter synchronous calls are not guarded (their
+                                          // save + check would cost a few % of the call)
+int guarded_chunk(rb_world *w, int64_t &K, int64_t left, bool opt, double dt, double e, double mu,
+                  const std::function<int(int64_t, bool)> &replay);
 int snapshot_to_host(rb_world *w, std::vector<double> &rows);
 int refit_from_device(rb_world *w, bool force = true);
-int enqueue_steps(rb_world *w, int64_t nsteps, double dt, double e, double mu, double thr, bool sharded = false);
 
 // ---- rb_api_tiles.hip --------------------------------------------------------
 constexpr int TILE_DECLINED = 1;   // tile_run: the auto mode gave the form up; the world steps hashed

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rb_tablegeom.hpp"   // the table's geometry constants (HIP-free: the host's world plan shares them)
+
 namespace rb {
 
 // error bits accumulated in the world's device error word
@@ -50,9 +52,6 @@ template <typename T> struct alignas(4 * sizeof(T)) Snap { T x, y, z, r; };
 // further ids of each follow in the block's other lines.  With R > 1 the
 // heads of neighbouring cells share lines (under the linear cell layout,
 // x-adjacent cells are adjacent buckets): fewer lines fetched per step.
-constexpr int LINE_WORDS = 32;               // uint32 words per bucket (head + further ids)
-constexpr int HEAD_WORDS = 2;                // the header's words
-constexpr int BUCKET_SLOTS = LINE_WORDS - HEAD_WORDS;
 constexpr uint32_t BOX_FLAG = 0x80000000u;   // set on ids of box bodies
 // The words a step kernel's lead needs, in one 16-byte-aligned device
 // allocation (rb_host.hpp lead_blk): {gen[0], gen[1], ctrl[0], ctrl[1]} — the
@@ -72,15 +71,6 @@ template <typename T> struct Table {
                                // << 32 | count) and SPILL_PAIRS {bucket, tagged id}, a bucket's line
                                // by hash (rb_grid.hpp spill_insert); nullptr: none (an overflow is an error)
 };
-// A bucket holds 30 ids; a cell with more (a pile-up: C4's sliding rows
-// reach 29 by step 700) spills the rest into its table's spill lines: the
-// line of the bucket's hash, or the next ones while it is full.  A search
-// reads a bucket's spill line(s) only when its count passed its slots.
-constexpr int SPILL_LINE_WORDS = 32;
-constexpr int SPILL_PAIRS = (SPILL_LINE_WORDS - 2) / 2;   // 15 per line
-constexpr int SPILL_LINES = 4096;                         // 512 KB per table
-constexpr int SPILL_PROBES = 64;                          // lines tried from the hashed one (<= 960 ids of a bucket)
-constexpr int SPILL_GROUP = 1;                            // lines a scan reads per round trip
 
 constexpr int MAX_PLANES = 8;
 
@@ -221,8 +211,6 @@ struct HaloPush {
 constexpr uint32_t EP_TAB = 1u, EP_APPEND = 2u, EP_DIRTY = 4u;
 constexpr int EP_AGE_SHIFT = 8, EP_LEN_SHIFT = 16, EP_START_SHIFT = 24;
 constexpr uint32_t EP_START_REBUILDS = 32, EP_START_LEN = 2;
-constexpr int EPOCH_MAX = 64;                // largest RBHIP_TABLE_EPOCH
-constexpr int EPOCH_DEFAULT = 8;             // (the measured choice)
 __host__ __device__ inline uint32_t epoch_word(uint32_t tab, uint32_t age, uint32_t len, bool dirty, uint32_t start) {
     return (tab & 1u) | (age + 1u < len ? EP_APPEND : 0u) | (dirty ? EP_DIRTY : 0u) | (age << EP_AGE_SHIFT) |
            (len << EP_LEN_SHIFT) | (start << EP_START_SHIFT);
@@ -561,15 +549,5 @@ template <typename T> hipError_t launch_batch_bound(Snap<T> *snap, const T *boun
 #define RB_STEP_BLOCK 64
 #endif
 constexpr int STEP_BLOCK = RB_STEP_BLOCK;
-
-// lanes per body of the split form's search kernel (1, or 8 = the
-// cooperative search, which reads the bucket slot snapshots)
-#ifndef RB_SPLIT_G
-#define RB_SPLIT_G 1
-#endif
-constexpr int SPLIT_SEARCH_LANES = RB_SPLIT_G;
-
-// does a world stepping with these forms need bucket slot snapshots?
-inline bool needs_slot_snapshots(bool coop, bool split) { return coop || (split && SPLIT_SEARCH_LANES > 1); }
 
 }  // namespace rb
