@@ -224,6 +224,57 @@ int rb_query_contacts_dev(rb_world *w, int64_t first, int64_t count, int32_t max
                           int32_t *counts, int32_t *partner, int32_t *kind,
                           void *dist, void *pos, void *frame, int32_t io_dtype);
 
+/* ---- the impulses of the next step -------------------------------------- */
+/* rb_batch_impulses (below) for one environment that is the world: for the
+ * world's current state and the step parameters of the call, what the next
+ * rb_step(w, 1, dt, ...) does to each body of [first, first + count).  jn, jt,
+ * vel and net mean what they mean there (the skip rules, a separating contact,
+ * the step's normal, the sums of net from +0; vel: the words the next
+ * rb_step(1, ...) writes into the body's qvel, whichever step form runs it).
+ * Applied forces (rb_set_xfrc, rb_set_xfrc_dev) are honoured by the path the
+ * step takes: once forces are set, the applied-force path for all-zero rows too.
+ *
+ * Layout: rb_query_contacts', dense, R = max_records slots per body.  counts
+ * [count]; partner, kind, dist and jn [count][R]; jt [count][R][3]; vel and
+ * net [count][6].  counts, partner, kind and dist are word for word what
+ * rb_query_contacts writes for the same state, range and R (the true count
+ * past R; kind -1 and zeros in the unused slots, in jn and jt as well).
+ * Truncation drops records only: vel and net do not depend on R.  partner,
+ * kind, dist, jn and jt are given all together with R > 0, or are all NULL
+ * with R 0 (the "sensor only" call); counts is required; vel and net may each
+ * be NULL.
+ *
+ * A body without a list (rb_query_contacts' three conditions) has counts -2,
+ * unused slots, and zero rows in vel and net.  The host form returns what
+ * rb_query_contacts returns there, all arrays written; the device form reports
+ * through counts alone; nothing sticky is set and the world's error word is
+ * untouched.  The query is pure exactly as rb_query_contacts is, and shares
+ * its table and its staging buffer.
+ *
+ * RB_EINVAL, nothing enqueued: every case of rb_query_contacts (the five record
+ * arrays all together or none); what rb_step refuses (dt not positive, a
+ * negative restitution, friction or contact_threshold, NaN); a non-finite dt,
+ * restitution, friction or contact_threshold.  RB_EUNSUPPORTED: world_size > 1;
+ * RB_LAW_BALLS; the device form under a stream capture.  count 0 is RB_OK.
+ *
+ * rb_query_impulses: host arrays, synchronous, staged and cut into sub-ranges
+ * of bodies as rb_query_contacts is (RBHIP_CONTACT_STAGE_BYTES); *n_truncated
+ * (may be NULL) = the listed bodies with count > max_records.
+ * rb_query_impulses_dev: device arrays, enqueued on the world's stream as
+ * rb_query_contacts_dev is; pointers are checked on the host; reals are of
+ * io_dtype, converted by a C cast.
+ *
+ * Not covered: sharded worlds; the two-ball law; impulses recorded inside a
+ * sampled run. */
+int rb_query_impulses(rb_world *w, int64_t first, int64_t count, int32_t max_records,
+                      double dt, double restitution, double friction, double contact_threshold,
+                      int32_t *counts, int32_t *partner, int32_t *kind, double *dist,
+                      double *jn, double *jt, double *vel, double *net, int64_t *n_truncated);
+int rb_query_impulses_dev(rb_world *w, int64_t first, int64_t count, int32_t max_records,
+                          double dt, double restitution, double friction, double contact_threshold,
+                          int32_t *counts, int32_t *partner, int32_t *kind, void *dist,
+                          void *jn, void *jt, void *vel, void *net, int32_t io_dtype);
+
 /* ---- the hot path ------------------------------------------------------ */
 /* nsteps reference steps: contact generation (mj_forward's role,
  * collision.py:57), gravity (collision.py:66-70), the per-contact
@@ -826,7 +877,8 @@ int  rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, in
  * host; reals are of io_dtype, converted by a C cast.  Not offered under a
  * stream capture.
  *
- * Not covered: the same query for an rb_world; impulses recorded inside
+ * Not covered: the same query for an rb_world of more than one rank (a world
+ * of one rank has it: rb_query_impulses); impulses recorded inside
  * rb_batch_run_sampled; the two-ball law. */
 int  rb_batch_impulses(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t max_records,
                        double dt, double restitution, double friction, double contact_threshold,

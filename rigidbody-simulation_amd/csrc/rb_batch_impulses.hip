@@ -45,16 +45,8 @@
 namespace rb {
 namespace {
 
-// is body b (kind) geom1 of its pair with body j (kind kj)?  The sphere of a
-// sphere-box pair, else the lower id: the rule by which contacts_pair orders
-// its operands (rb_contacts.hpp) and the step flips the normal (rb_body.hpp
-// solve_sphere_pair, rb_batch_body.hpp solve_box_pair).  Those keep the rule
-// inside and hand no flag to emit, so the query states it here, once for all
-// its instances.
-__device__ __forceinline__ bool self_is_geom1(int32_t kind, int32_t kj, int b, int j) {
-    return (kind == 0 && kj != 0) || ((kind != 0) == (kj != 0) && b < j);
-}
-
+// (self_is_geom1, the flag the contact lambda below takes: rb_contacts.hpp)
+//
 // Lane threadIdx.x of a workgroup of BLOCK threads is body b of the environment
 // of row `row` of the query, whose bodies sit in the LDS slots from ebase on;
 // in_range: the lane has a row and a body slot (else it loads slot 0's data and

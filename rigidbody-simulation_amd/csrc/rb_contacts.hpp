@@ -75,6 +75,16 @@ __device__ __forceinline__ void contacts_planes(int32_t n_planes, Plane plane, i
     }
 }
 
+// is body b (kind) geom1 of its pair with body j (kind kj)?  The sphere of a
+// sphere-box pair, else the lower id: the rule by which contacts_pair orders
+// its operands and the step flips the normal (rb_body.hpp solve_sphere_pair,
+// rb_batch_body.hpp solve_box_pair).  Those keep the rule inside and hand no
+// flag to emit, so the impulse queries (rb_batch_impulses.hip,
+// rb_world_impulses.hip) read it here.
+__device__ __forceinline__ bool self_is_geom1(int32_t kind, int32_t kj, int b, int j) {
+    return (kind == 0 && kj != 0) || ((kind != 0) == (kj != 0) && b < j);
+}
+
 // Body b (kind, centre x, half extents sz, bounding radius bi, orientation
 // Mi) against body j (kind kj, snapshot sj): two spheres by the step kernels'
 // test (sphere_sphere_hit), a box-involved pair (BOXES instances only) by

@@ -1,4 +1,4 @@
-// rb_stagelayout.hpp — how the host form of a query (rb_query_contacts,
+// rb_stagelayout.hpp — how the host form of a query (rb_query_contacts, rb_query_impulses,
 // rb_batch_contacts, rb_batch_impulses) lays its arrays out in the staging
 // buffer.  HIP-free: plain host C++ (tests/host_stagelayout.cpp).
 //
@@ -62,8 +62,8 @@ inline StageLayout stage_contacts(size_t bodies, int32_t R, bool pos, bool frame
     return l;
 }
 
-// The impulse records of environments of M bodies, R slots per body.  vel,
-// net: given by the caller.
+// The impulse records of environments of M bodies (a world's body: M 1), R
+// slots per body.  vel, net: given by the caller.
 enum { SI_DIST, SI_JN, SI_JT, SI_VEL, SI_NET, SI_COUNTS, SI_PARTNER, SI_KIND, SI_FIELDS };
 inline StageLayout stage_impulses(size_t M, int32_t R, bool vel, bool net) {
     const size_t slots = M * (size_t)R;

@@ -13,7 +13,7 @@ way the reference puts its repo root on PYTHONPATH for `src.*`).
 from . import scenes  # noqa: F401
 from ._lib import RbError, load  # noqa: F401
 from .batch import BatchContacts, BatchImpulses, BatchWorld  # noqa: F401
-from .world import World, WorldContacts, kat_apply, kat_impulse, kat_inertia, kat_narrow, kat_pair_impulse  # noqa: F401
+from .world import World, WorldContacts, WorldImpulses, kat_apply, kat_impulse, kat_inertia, kat_narrow, kat_pair_impulse  # noqa: F401
 
 __all__ = ["World", "BatchWorld", "RbError", "load", "scenes", "kat_impulse", "kat_inertia", "kat_apply", "kat_pair_impulse",
            "kat_narrow"]

@@ -69,6 +69,9 @@ def _pair_typestr(own, names, arrays, dtype):
 # callers pass `*ptrs.values()`, so a new field goes where the C-ABI has it.
 _CONTACT_FIELDS = (("counts", False, (), False), ("partner", True, (), False), ("kind", True, (), False),
                    ("dist", True, (), True), ("pos", True, (3,), True), ("frame", True, (3,), True))
+# the arrays of an impulse query (rb_batch_impulses, rb_query_impulses)
+_IMPULSE_FIELDS = _CONTACT_FIELDS[:4] + (("jn", True, (), True), ("jt", True, (3,), True),
+                                         ("vel", False, (6,), True), ("net", False, (6,), True))
 
 
 def _field_shape(field, lead, R):

@@ -56,6 +56,8 @@ SIGNATURES = {
     "rb_set_xfrc_dev": (C.c_int, [_P, _P, _I32]),
     "rb_query_contacts": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, C.POINTER(_I64)]),
     "rb_query_contacts_dev": (C.c_int, [_P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _I32]),
+    "rb_query_impulses": (C.c_int, [_P, _I64, _I64, _I32, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I64)]),
+    "rb_query_impulses_dev": (C.c_int, [_P, _I64, _I64, _I32, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "rb_step": (C.c_int, [_P, _I64, _D, _D, _D, _D]),
     "rb_step_async": (C.c_int, [_P, _I64, _D, _D, _D, _D]),
     "rb_sync": (C.c_int, [_P]),

@@ -41,14 +41,9 @@ from typing import Any, Optional
 import numpy as np
 
 from . import _lib
-from ._devarray import (_CONTACT_FIELDS, _IO_CODES, _device_array, _host_arrays, _new_tensor, _pair_typestr,
-                        _resolve_out)
+from ._devarray import (_CONTACT_FIELDS, _IMPULSE_FIELDS, _IO_CODES, _device_array, _host_arrays, _new_tensor,
+                        _pair_typestr, _resolve_out)
 from .scenes import Scene
-
-
-# the arrays of the impulse query (_devarray._CONTACT_FIELDS: name, record, tail, real)
-_IMPULSE_FIELDS = _CONTACT_FIELDS[:4] + (("jn", True, (), True), ("jt", True, (3,), True),
-                                         ("vel", False, (6,), True), ("net", False, (6,), True))
 
 
 class BatchContacts:

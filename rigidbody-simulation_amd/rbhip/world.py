@@ -14,8 +14,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._devarray import (_CONTACT_FIELDS, _IO_CODES, _device_array, _host_arrays, _new_tensor, _pair_typestr,
-                        _resolve_out)
+from ._devarray import (_CONTACT_FIELDS, _IMPULSE_FIELDS, _IO_CODES, _device_array, _host_arrays, _new_tensor,
+                        _pair_typestr, _resolve_out)
 from .scenes import Scene
 
 COMM_ID_BYTES = 128      # ncclUniqueId (rccl.h NCCL_UNIQUE_ID_BYTES)
@@ -64,6 +64,35 @@ class WorldContacts:
         for a in (self.partner, self.kind, self.dist, self.pos, self.frame):
             out.append(None if a is None else np.asarray(a).reshape((cnt.size, R) + np.shape(a)[3:])[keep])
         return tuple(out)
+
+
+class WorldImpulses:
+    """What the next step does to each listed body of a world, contact by
+    contact (World.query_impulses / query_impulses_device): the fields of
+    BatchImpulses for one row, dense arrays with R = max_records slots per body.
+
+    counts (1, count), partner, kind, dist (1, count, R): word for word the
+    fields of WorldContacts for the same state, range and R (-2 in counts for a
+    body without a list).  jn (1, count, R), jt (1, count, R, 3): the two
+    return values of compute_collision_impulse_friction (collision.py:7-48)
+    for the contact, 0 where the step skips it or it separates.  vel
+    (1, count, 6): (v, omega) after gravity, applied forces and all the body's
+    contacts, the qvel of the next step(1).  net (1, count, 6): the body's net
+    contact impulse and net angular impulse about its centre.  vel and net do
+    not depend on R; a body without a list has zero rows.  With max_records 0
+    the five record fields are None (the "sensor only" call).  truncated: the
+    bodies with count > R (None for the device form, which does not wait).
+    first: the id of the first listed body."""
+
+    def __init__(self, counts, partner, kind, dist, jn, jt, vel, net, truncated, first=0):
+        self.counts, self.partner, self.kind, self.dist = counts, partner, kind, dist
+        self.jn, self.jt, self.vel, self.net = jn, jt, vel, net
+        self.truncated = truncated
+        self.first = first
+
+    @property
+    def max_records(self) -> int:
+        return 0 if self.partner is None else int(self.partner.shape[-1])
 
 
 class World:
@@ -331,16 +360,17 @@ class World:
         _lib.check(self._L.rb_record_contacts(self._h, int(bool(enable))), "rb_record_contacts")
 
     # ---- the contact query ---------------------------------------------------
-    def _query_range(self, first, count, max_records, geometry):
+    def _query_range(self, first, count, max_records, per_slot, per_body=4):
+        """per_slot, per_body: the bytes of one record slot and of one body's
+        own words in the host form's staging buffer."""
         n = self.scene.n
         first = int(first)
         count = n - first if count is None else int(count)
         if max_records is None:
             # the scene's bound, as long as one body's slots fit the staging
-            # buffer of the host form (rb_query_contacts)
+            # buffer of the host form (rb_query_contacts, rb_query_impulses)
             R = 4 * self._n_planes + (4 if self._any_box else 1) * QUERY_PARTNERS
-            per_slot = 8 * (7 if geometry else 1) + 8
-            R = max(0, min(R, (self._stage_limit - 4) // per_slot))
+            R = max(0, min(R, (self._stage_limit - per_body) // per_slot))
         else:
             R = int(max_records)
         return first, count, R
@@ -357,7 +387,7 @@ class World:
         raises RbError (EOVERFLOW / EDOM) if strict; with strict=False the
         arrays are returned with -2 in its counts.  One rank, not under
         "balls"."""
-        first, count, R = self._query_range(first, count, max_records, geometry)
+        first, count, R = self._query_range(first, count, max_records, 8 * (7 if geometry else 1) + 8)
         c = max(count, 0)
         a = _host_arrays(_CONTACT_FIELDS, (1, c), R, skip=() if geometry else ("pos", "frame"))
         nt = C.c_int64()
@@ -378,7 +408,8 @@ class World:
         arrays', else the world's).  truncated is None: nothing is read back,
         and a body without a list shows as -2 in counts alone."""
         # (with `out` its partner sets R: only first and count are taken here, `bound` is unused)
-        first, count, bound = self._query_range(first, count, max_records if out is None else 0, geometry)
+        first, count, bound = self._query_range(first, count, max_records if out is None else 0,
+                                                8 * (7 if geometry else 1) + 8)
         c = max(count, 0)
         R, ts, given, ptrs = _resolve_out(
             _CONTACT_FIELDS, (1, c), ("partner", "kind", "dist") if c > 0 else (),
@@ -387,6 +418,54 @@ class World:
         _lib.check(self._L.rb_query_contacts_dev(self._h, first, count, R, *ptrs.values(), _IO_CODES[ts]),
                    "rb_query_contacts_dev")
         return WorldContacts(R, *given.values(), None, first)   # (with R == 0 the library takes counts alone)
+
+    # ---- the impulses of the next step ----------------------------------------
+    _IMPULSE_SLOT, _IMPULSE_BODY = 5 * 8 + 8, 4 + 2 * 6 * 8      # staging bytes: a record slot; counts, vel and net
+
+    def query_impulses(self, first=0, count=None, max_records=None, dt=None, restitution=None, friction=None,
+                       threshold=None, strict=True) -> WorldImpulses:
+        """What the next step(1, dt, restitution, friction, threshold) does to
+        bodies [first, first + count) (count None: up to the last), contact by
+        contact: the contact list of query_contacts(), jn and jt of every
+        record (collision.py:7-48, :72-88), the velocity the solve leaves and
+        the body's net contact impulse, applied forces (set_xfrc) included.
+        It steps nothing and changes nothing a step can see; like get_state()
+        it first finishes the world's pending work.  max_records as for
+        query_contacts() (0: counts, vel and net only); the step parameters
+        default to the scene's, as for step().  A body whose list cannot be
+        built raises RbError if strict, as query_contacts() does.  One rank,
+        not under "balls"."""
+        first, count, R = self._query_range(first, count, max_records, self._IMPULSE_SLOT, self._IMPULSE_BODY)
+        p = self._params(dt, restitution, friction, threshold)
+        a = _host_arrays(_IMPULSE_FIELDS, (1, max(count, 0)), R)
+        nt = C.c_int64()
+        rc = self._L.rb_query_impulses(self._h, first, count, R, *p, *(_lib.ptr(v) for v in a.values()), C.byref(nt))
+        # (EOVERFLOW / EDOM of a query with valid arguments: a body without a list, every array written)
+        if rc != _lib.RB_OK and (strict or rc not in (-75, -33)):
+            _lib.check(rc, "rb_query_impulses")
+        return WorldImpulses(*a.values(), nt.value, first)
+
+    def query_impulses_device(self, first=0, count=None, max_records=None, dt=None, restitution=None, friction=None,
+                              threshold=None, dtype=None, out=None) -> WorldImpulses:
+        """query_impulses() into device memory, enqueued on the world's stream
+        without waiting, with the conventions of query_contacts_device(): a
+        WorldImpulses whose fields are the arrays of `out` (a WorldImpulses of
+        an earlier call, or a mapping with the fields' names; its max_records
+        holds; vel and net may be left out) or new torch tensors: counts,
+        partner and kind int32, the rest of `dtype` ("f64" / "f32"; None: the
+        arrays', else the world's).  truncated is None: nothing is read back,
+        and a body without a list shows as -2 in counts alone."""
+        first, count, bound = self._query_range(first, count, max_records if out is None else 0, self._IMPULSE_SLOT,
+                                                self._IMPULSE_BODY)
+        p = self._params(dt, restitution, friction, threshold)
+        c = max(count, 0)
+        R, ts, given, ptrs = _resolve_out(
+            _IMPULSE_FIELDS, (1, c), ("partner", "kind", "dist", "jn", "jt") if c > 0 else (),
+            "partner, kind, dist, jn and jt: all five with max_records > 0, none with 0", out, max_records, dtype,
+            self.dtype, self.device, lambda: bound, exclusive=True)
+        _lib.check(self._L.rb_query_impulses_dev(self._h, first, count, R, *p, *ptrs.values(), _IO_CODES[ts]),
+                   "rb_query_impulses_dev")
+        return WorldImpulses(*given.values(), None, first)
 
     def contacts(self):
         """Contact list of the most recent step, CSR over owned bodies:
