@@ -265,7 +265,9 @@ int rb_query_contacts_dev(rb_world *w, int64_t first, int64_t count, int32_t max
  * io_dtype, converted by a C cast.
  *
  * Not covered: sharded worlds; the two-ball law; impulses recorded inside a
- * sampled run. */
+ * sampled run of a world (a batch records the per-body net impulse:
+ * rb_batch_run_sampled_impulses; per-contact records jn, jt inside a sampled
+ * run are open for both). */
 int rb_query_impulses(rb_world *w, int64_t first, int64_t count, int32_t max_records,
                       double dt, double restitution, double friction, double contact_threshold,
                       int32_t *counts, int32_t *partner, int32_t *kind, double *dist,
@@ -501,7 +503,9 @@ int rb_kernel_timing(rb_world *w, int enable, double *avg_ms, int64_t *launches)
  * Arrays are environment-major: body k of environment e at row e*M + k.
  * Not covered (use rb_world): contacts recorded inside a step (a batch is
  * asked for the contact list of its current state: rb_batch_contacts, and for
- * the impulses of its next step: rb_batch_impulses), sharding,
+ * the impulses of its next step: rb_batch_impulses; a sampled run records
+ * each body's net contact impulse per window: rb_batch_run_sampled_impulses;
+ * per-contact records jn, jt inside a sampled run are open), sharding,
  * per-environment plane counts, more than 256 bodies per
  * environment; under RB_LAW_BALLS also per-environment planes, applied
  * forces, the contact query, environments of more than 64 bodies and
@@ -878,8 +882,10 @@ int  rb_batch_contacts_dev(rb_batch *b, int32_t max_records, int32_t *counts, in
  * stream capture.
  *
  * Not covered: the same query for an rb_world of more than one rank (a world
- * of one rank has it: rb_query_impulses); impulses recorded inside
- * rb_batch_run_sampled; the two-ball law. */
+ * of one rank has it: rb_query_impulses); per-contact records (jn, jt) inside
+ * a sampled run (the per-body net impulse is recorded there:
+ * rb_batch_run_sampled_impulses), and either for an rb_world; the two-ball
+ * law. */
 int  rb_batch_impulses(rb_batch *b, const int64_t *env_ids, int64_t n, int32_t max_records,
                        double dt, double restitution, double friction, double contact_threshold,
                        int32_t *counts, int32_t *partner, int32_t *kind, double *dist,
@@ -888,6 +894,65 @@ int  rb_batch_impulses_dev(rb_batch *b, int32_t max_records,
                            double dt, double restitution, double friction, double contact_threshold,
                            int32_t *counts, int32_t *partner, int32_t *kind, void *dist,
                            void *jn, void *jt, void *vel, void *net, int32_t io_dtype);
+
+/* ---- contact-impulse curves of a sampled run (additive to librbhip 0.4) --------
+ * rb_batch_run_sampled that also records what the contacts did to every body
+ * between two samples: the force curve of the run (the ground reaction of a
+ * bouncing ball, the load on the bottom cube of a stack) beside the curves the
+ * reference's loggers plot.  Stepping, the S = nsteps / every samples, qpos
+ * [S][n_envs][M][7], qvel [S][n_envs][M][6], final state, status, steps_done and
+ * failure semantics are rb_batch_run_sampled's, word for word.
+ *
+ * net [S][n_envs][M][6]: row (s, e, k) is the contact impulse (components 0-2)
+ * and the angular impulse about its centre (3-5) that body k of environment e
+ * received in the window of sample s, steps s * every + 1 .. (s + 1) * every of
+ * this call.  It is defined by rb_batch_impulses: for each committed step of
+ * the window, that step's net row for the state the step starts from (the sum
+ * of P = jn n + jt, the two return values of compute_collision_impulse_friction,
+ * collision.py:7-48, and of r x P, over the applied contacts of the per-body
+ * loop, collision.py:72-88, in list order from +0, P as
+ * apply_impulse_friction evaluates it, physics_utils.py:25-49); these rows
+ * added component by component, in step order, from +0, in the batch's real
+ * type.  net[s][e][k][0:3] / (every * dt) is the window's average contact force;
+ * with every == 1 a row is the word rb_batch_impulses returns before that step.
+ * A step that is not committed contributes nothing (the failing step of an
+ * environment and every later one): the window that holds the failure keeps the
+ * sum of its committed steps, later windows are rows of +0.  Rows of absent
+ * bodies of a population are +0.  Steps after the last sample are run and
+ * belong to no window.  Step parameters, per-environment parameters, planes,
+ * gravity, applied forces and a population are honoured as the step honours
+ * them.
+ *
+ * The sums are kept in the step kernel's register loop and do not depend on
+ * how the run is cut into launches (RB_BATCH_CHUNK steps at most, fewer where
+ * the sample buffer fills): a window left open by a launch is carried in a
+ * per-batch device buffer of 6 * n_envs * M reals.
+ *
+ * net is required when S > 0.  qpos and qvel may each be NULL: a sample takes
+ * rows = 6 + (qpos ? 7 : 0) + (qvel ? 6 : 0) struct-of-arrays rows of the
+ * buffer, n_envs * M * rows * (sizeof(real) + 8) bytes in the host form and
+ * n_envs * M * rows * sizeof(real) in the device form, under
+ * RBHIP_BATCH_SAMPLE_BYTES.
+ * RB_EINVAL (nothing stepped) as rb_batch_run_sampled, with net in the place
+ * of qpos: every < 1, nsteps < 0, what rb_batch_step refuses, net NULL with
+ * S > 0, a buffer bound below one sample; in the device form a host pointer or
+ * memory of another device, or an unknown io_dtype.  RB_EUNSUPPORTED under
+ * RB_LAW_BALLS, changing nothing.
+ *
+ * rb_batch_run_sampled_impulses: host arrays, synchronous, reports through
+ * n_failed as rb_batch_run_sampled does.
+ * rb_batch_run_sampled_impulses_dev: device arrays of io_dtype (converted by a
+ * C cast), enqueued on the batch's stream without waiting, no report
+ * (rb_batch_sync).  Not offered under a stream capture.
+ *
+ * Not covered: per-contact records (jn, jt) inside a sampled run; the same
+ * for an rb_world; the two-ball law. */
+int  rb_batch_run_sampled_impulses(rb_batch *b, int64_t nsteps, int64_t every, double dt, double restitution,
+                                   double friction, double contact_threshold,
+                                   double *qpos, double *qvel, double *net, int64_t *n_failed);
+int  rb_batch_run_sampled_impulses_dev(rb_batch *b, int64_t nsteps, int64_t every, double dt, double restitution,
+                                       double friction, double contact_threshold,
+                                       void *qpos, void *qvel, void *net, int32_t io_dtype);
 
 /* Retired (kept for ABI compatibility with librbhip 0.2): the round-3 tile
  * blocks' configuration.  mode -1 (auto) and 0 (off) are accepted and do

@@ -1,9 +1,11 @@
 // rb_api_batch.hip — batched worlds: lifetime (rb_batch_create*,
 // rb_batch_destroy), the setters (rb_batch_set_params / _bodies / _population /
 // _contact_law / _planes / _gravity / _xfrc), rb_batch_set_state and
-// rb_batch_get_state, rb_batch_step, rb_batch_run_sampled and rb_batch_status.
+// rb_batch_get_state, rb_batch_step, rb_batch_run_sampled,
+// rb_batch_run_sampled_impulses and rb_batch_status.
 // Kernels: rb_batch.hip, rb_batch_boxes.hip and, for an environment of more
-// than 64 bodies, rb_batch_wide.hip; with a population set, rb_batch_ragged.hip.
+// than 64 bodies, rb_batch_wide.hip; with a population set, rb_batch_ragged.hip;
+// a sampled run that records impulse curves, rb_batch_sensed.hip.
 // E replicas of a template environment of M <= 256 bodies, body b of
 // environment e at slot e * M + b of every device row.  All work is enqueued
 // on the batch's stream (its own, or the caller's: rb_batch_set_stream); the
@@ -26,7 +28,7 @@ void free_batch(rb_batch *b) {
     (void)hipSetDevice(b->device);
     if (b->own_stream) (void)hipStreamSynchronize(b->stream);
     void *bufs[] = {b->snap, b->state, b->consts, b->env_e, b->env_mu, b->code, b->count, b->steps_done,
-                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused, b->con, b->pop.tables};
+                    b->io_q, b->io_v, b->ids, b->samp, b->env_planes, b->env_g, b->env_xfrc, b->d_kind, b->refused, b->con, b->sense, b->pop.tables};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);   // (never the caller's)
@@ -550,6 +552,46 @@ int rb_batch_run_sampled(rb_batch *b, int64_t nsteps, int64_t every, double dt, 
         const size_t n = (size_t)l.drain * N, at = (size_t)l.drain_at * N;
         HIPCHK(hipMemcpyAsync(qpos + 7 * at, out_q, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, b->stream));
         if (qvel) HIPCHK(hipMemcpyAsync(qvel + 6 * at, out_v, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return batch_report(b, n_failed);
+}
+
+int rb_batch_run_sampled_impulses(rb_batch *b, int64_t nsteps, int64_t every, double dt, double e, double mu, double thr,
+                                  double *qpos, double *qvel, double *net, int64_t *n_failed) {
+    ApiScope api_scope_(b ? b->device : -1);
+    SampledRun r;
+    WCHK(batch_sensed_prelude(b, nsteps, every, dt, e, mu, thr, qpos, qvel, net, nullptr, sample_bytes, r));
+    if (nsteps / every == 0) {         // no window: nothing to sense
+        WCHK(batch_enqueue_steps(b, nsteps, dt, e, mu, thr));
+        return batch_report(b, n_failed);
+    }
+    // the slots first, the boundary rows of `fit` samples behind them: qpos, qvel (those asked for), net
+    const size_t N = (size_t)b->N, fit = (size_t)r.fit;
+    const int rows = r.rows;
+    char *slots = b->samp;
+    double *out = reinterpret_cast<double *>(b->samp + align8(fit * N * rows * b->esz));
+    double *out_q = qpos ? out : nullptr;
+    double *out_v = qvel ? out + fit * N * (qpos ? 7 : 0) : nullptr;
+    double *out_n = out + fit * N * (size_t)(rows - 6);
+    const SensedRun sr = batch_sensed_run(b, qpos != nullptr, qvel != nullptr);
+    HIPCHK(hipMemsetAsync(b->sense, 0, N * 6 * (size_t)b->esz, b->stream));   // the first window starts from +0
+
+    SamplePlan plan(nsteps, every, BATCH_CHUNK, r.fit);
+    SampleLaunch l;
+    while (plan.next(l)) {
+        WCHK(batch_enqueue_sensed(b, l, slots, r, sr, every, dt, e, mu, thr));
+        if (l.drain == 0) continue;
+        // a plain synchronous drain: transpose, download, wait
+        HIPCHK(by_real(b->dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_sensed_out<T, double>(reinterpret_cast<const T *>(slots), (int32_t)l.drain, rows, sr, b->N, out_q,
+                                                out_v, out_n, b->stream);
+        }));
+        const size_t n = (size_t)l.drain * N, at = (size_t)l.drain_at * N;
+        if (qpos) HIPCHK(hipMemcpyAsync(qpos + 7 * at, out_q, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, b->stream));
+        if (qvel) HIPCHK(hipMemcpyAsync(qvel + 6 * at, out_v, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(net + 6 * at, out_n, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
     }
     return batch_report(b, n_failed);

@@ -1,7 +1,9 @@
 // rb_api_batch_dev.hip — the enqueue side of a batch.  First what every launch
 // shares: the kernels' argument block (batch_params), the step launches
-// (batch_enqueue_steps) and a sampled run's prelude and launches, which
-// rb_batch_step and rb_batch_run_sampled wait for and the entries here do not.
+// (batch_enqueue_steps) and a sampled run's prelude and launches (with them
+// those of a run that records impulse curves: batch_sensed_prelude,
+// batch_enqueue_sensed), which rb_batch_step, rb_batch_run_sampled and
+// rb_batch_run_sampled_impulses wait for and the entries here do not.
 // Then the device-resident boundary (rb_batch_set_stream, rb_batch_step_async,
 // rb_batch_sync, rb_batch_*_dev but the queries'; kernels in rb_batch_dev.hip):
 // the caller's arrays are device memory on the batch's device, every entry but
@@ -121,6 +123,60 @@ int batch_enqueue_sampled(rb_batch *b, const SampleLaunch &l, char *slots, const
             if (rc != hipSuccess) return rc;
         }
         return batch_launch<T>(b, p, true);
+    }));
+    return RB_OK;
+}
+
+int batch_sensed_prelude(rb_batch *b, int64_t nsteps, int64_t every, double dt, double e, double mu, double thr,
+                         const void *qpos, const void *qvel, const void *net, const int32_t *io_dtype,
+                         size_t (*per)(const rb_batch *, int rows), SampledRun &r) {
+    WCHK(batch_check_step(b, nsteps, dt, e, mu, thr));
+    if (every < 1) return fail(RB_EINVAL, "every must be >= 1");
+    if (io_dtype) WCHK(batch_check_io(*io_dtype));
+    if (b->law == RB_LAW_BALLS)
+        return fail(RB_EUNSUPPORTED, "the two-ball law records no impulse curves (it has no contact list: rb_batch_impulses)");
+    const int64_t S = nsteps / every;
+    if (S > 0 && !net) return fail(RB_EINVAL, "net NULL with %lld samples to record", (long long)S);
+    HIPCHK(hipSetDevice(b->device));
+    r.rows = sensed_rows(qpos != nullptr, qvel != nullptr);
+    r.fit = 1;
+    if (S == 0) return RB_OK;
+    if (io_dtype) WCHK(dev_ptrs(b->device, "batch", {{qpos, "qpos"}, {qvel, "qvel"}, {net, "net"}}));
+    const size_t bytes = per(b, r.rows);
+    if (bytes > b->samp_limit)
+        return fail(RB_EINVAL, "one sample of the batch (%zu bytes) does not fit the sample buffer (%zu bytes: "
+                               "RBHIP_BATCH_SAMPLE_BYTES)", bytes, b->samp_limit);
+    r.fit = std::min<int64_t>({S, (int64_t)(b->samp_limit / bytes), (int64_t)INT32_MAX / 2});
+    WCHK(grow((void **)&b->samp, &b->samp_bytes, bytes * (size_t)r.fit));
+    return grow(&b->sense, &b->sense_bytes, (size_t)b->N * 6 * (size_t)b->esz);
+}
+
+SensedRun batch_sensed_run(const rb_batch *b, bool want_q, bool want_v) {
+    // (with a population the kinds are the population's: no one-box instance)
+    return sensed_run(b->sense, b->box && !b->pop.set, want_q, want_v);
+}
+
+int batch_enqueue_sensed(rb_batch *b, const SampleLaunch &l, char *slots, const SampledRun &r, const SensedRun &sr,
+                         int64_t every, double dt, double e, double mu, double thr) {
+    HIPCHK(by_real(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        BatchParams<T> p = batch_params<T>(b, (int32_t)l.steps, dt, e, mu, thr);
+        p.samp = reinterpret_cast<T *>(slots);
+        // phase and period travel as int32, clamped per launch as batch_enqueue_sampled clamps them; a
+        // launch without a sample (its phase lies past its steps) senses all the same: the window runs on
+        p.every = (int32_t)std::min<int64_t>(every, BATCH_CHUNK + 1);
+        p.phase = (int32_t)std::min<int64_t>(l.phase, BATCH_CHUNK + 1);
+        p.samp_first = (int32_t)l.first;
+        p.samp_slots = (int32_t)r.fit;
+        p.samp_rows = r.rows;
+        // absent bodies store nothing: their rows of the slots this launch fills hold zeros
+        if (b->pop.set && b->pop.absent && l.samples > 0) {
+            const size_t slot = (size_t)b->N * (size_t)r.rows * sizeof(T);
+            const hipError_t rc = hipMemsetAsync(slots + (size_t)l.first * slot, 0, (size_t)l.samples * slot, b->stream);
+            if (rc != hipSuccess) return rc;
+        }
+        if (b->pop.set) return launch_batch_sensed<T>(p, batch_population(b), sr, b->pop.boxes, b->stream);
+        return launch_batch_sensed<T>(p, Population{}, sr, b->mixed, b->stream);
     }));
     return RB_OK;
 }
@@ -272,6 +328,32 @@ int rb_batch_run_sampled_dev(rb_batch *b, int64_t nsteps, int64_t every, double 
             using IO = decltype(io);
             return launch_dev_samples_out<T, IO>(reinterpret_cast<const T *>(b->samp), (int32_t)l.drain, r.rows, b->N,
                                                  (IO *)qpos + 7 * at, qvel ? (IO *)qvel + 6 * at : nullptr, b->stream);
+        }));
+    }
+    return RB_OK;
+}
+
+int rb_batch_run_sampled_impulses_dev(rb_batch *b, int64_t nsteps, int64_t every, double dt, double e, double mu,
+                                      double thr, void *qpos, void *qvel, void *net, int32_t io_dtype) {
+    ApiScope api_scope_(b ? b->device : -1);
+    SampledRun r;
+    WCHK(batch_sensed_prelude(b, nsteps, every, dt, e, mu, thr, qpos, qvel, net, &io_dtype, slot_bytes, r));
+    if (nsteps / every == 0) return batch_enqueue_steps(b, nsteps, dt, e, mu, thr);   // no window: nothing to sense
+    const size_t N = (size_t)b->N;
+    const SensedRun sr = batch_sensed_run(b, qpos != nullptr, qvel != nullptr);
+    HIPCHK(hipMemsetAsync(b->sense, 0, N * 6 * (size_t)b->esz, b->stream));           // the first window starts from +0
+    SamplePlan plan(nsteps, every, BATCH_CHUNK, r.fit);
+    SampleLaunch l;
+    while (plan.next(l)) {
+        WCHK(batch_enqueue_sensed(b, l, b->samp, r, sr, every, dt, e, mu, thr));
+        if (l.drain == 0) continue;
+        const size_t at = (size_t)l.drain_at * N;
+        HIPCHK(by_real_io(b, io_dtype, [&](auto t, auto io) {
+            using T = decltype(t);
+            using IO = decltype(io);
+            return launch_sensed_out<T, IO>(reinterpret_cast<const T *>(b->samp), (int32_t)l.drain, r.rows, sr, b->N,
+                                            qpos ? (IO *)qpos + 7 * at : nullptr, qvel ? (IO *)qvel + 6 * at : nullptr,
+                                            (IO *)net + 6 * at, b->stream);
         }));
     }
     return RB_OK;

@@ -3,6 +3,7 @@
 // and the functions that cross those units.  Not part of the public interface.
 #pragma once
 #include "rb_batch_ragged.hpp"
+#include "rb_batch_sensed.hpp"
 #include "rb_host.hpp"
 #include "rb_sampleplan.hpp"
 
@@ -53,6 +54,10 @@ struct rb_batch {
     // of listed environments (allocated on first use, at most samp_limit bytes)
     char *con = nullptr;
     size_t con_bytes = 0;
+    // rb_batch_run_sampled_impulses: the running window's partial sums, [6][E * M]
+    // reals, zeroed at the start of a call and carried from launch to launch
+    void *sense = nullptr;
+    size_t sense_bytes = 0;
     // the sizes last given (rb_batch_create, rb_batch_set_bodies): [E * M * 3];
     // a change of population derives the bounding radii from them again
     std::vector<double> size;
@@ -101,6 +106,18 @@ int batch_sampled_prelude(rb_batch *b, int64_t nsteps, int64_t every, double dt,
 // launch l of a sampled run's plan, recording into the r.fit slots at `slots`
 int batch_enqueue_sampled(rb_batch *b, const SampleLaunch &l, char *slots, const SampledRun &r, int64_t every, double dt,
                           double e, double mu, double thr);
+
+// The same two for a run that records impulse curves (rb_batch_run_sampled_impulses, _dev): net is the
+// required array, qpos and qvel may each be NULL; r.rows: sensed_rows(qpos, qvel).  RB_EUNSUPPORTED under
+// the two-ball law.  With samples to record the prelude also allocates the carry rows (b->sense); the
+// caller zeroes them before the first launch.  Every launch of the plan runs the sensing kernel.
+int batch_sensed_prelude(rb_batch *b, int64_t nsteps, int64_t every, double dt, double e, double mu, double thr,
+                         const void *qpos, const void *qvel, const void *net, const int32_t *io_dtype,
+                         size_t (*per)(const rb_batch *, int rows), SampledRun &r);
+int batch_enqueue_sensed(rb_batch *b, const SampleLaunch &l, char *slots, const SampledRun &r, const SensedRun &sr,
+                         int64_t every, double dt, double e, double mu, double thr);
+// the slot layout of such a run for this batch
+SensedRun batch_sensed_run(const rb_batch *b, bool want_q, bool want_v);
 
 int batch_check_io(int32_t io_dtype);
 

@@ -111,6 +111,8 @@ SIGNATURES = {
     "rb_batch_contacts_dev": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32]),
     "rb_batch_impulses": (C.c_int, [_P, _P, _I64, _I32, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I64)]),
     "rb_batch_impulses_dev": (C.c_int, [_P, _I32, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "rb_batch_run_sampled_impulses": (C.c_int, [_P, _I64, _I64, _D, _D, _D, _D, _P, _P, _P, C.POINTER(_I64)]),
+    "rb_batch_run_sampled_impulses_dev": (C.c_int, [_P, _I64, _I64, _D, _D, _D, _D, _P, _P, _P, _I32]),
 }
 
 # rb_world_stats indices (include/rbhip.h RB_STAT_*)

@@ -26,7 +26,9 @@ contact (jn and jt of collision.py:7-48, the velocity the solve leaves, the
 net contact impulse), without stepping.
 Arrays are environment-major: (E, M, 7) / (E, M, 6).  run_sampled() returns
 the curves the reference plots (logger_base.py, data_logger.py,
-multi_sphere_logger.py), one per environment, sampled on the device.
+multi_sphere_logger.py), one per environment, sampled on the device;
+run_sampled_impulses() adds the force curve of the same run, each body's
+contact impulse summed over every sampling window inside the step loop.
 
 The *_device methods keep all of that in device memory: they take any object
 with __cuda_array_interface__ (a torch tensor on the batch's GPU), enqueue on
@@ -404,6 +406,29 @@ class BatchWorld:
                    "rb_batch_run_sampled")
         return q, v, nf.value
 
+    def run_sampled_impulses(self, nsteps: int, every: int, positions: bool = True, velocities: bool = True, dt=None,
+                             restitution=None, friction=None, threshold=None):
+        """run_sampled() that also records the contact-impulse curve of the
+        run.  Returns (qpos (S, E, M, 7) or None, qvel (S, E, M, 6) or None,
+        net (S, E, M, 6), n_failed).  net[s, e, k] is the contact impulse
+        (0:3) and angular impulse about its centre (3:6) that body k of
+        environment e received over steps s * every + 1 .. (s + 1) * every of
+        this call: the sum, in step order, of the `net` row impulses() gives
+        before each committed step.  net[..., 0:3] / (every * dt) is the
+        window's average contact force.  A failed environment's windows after
+        the failure are zeros, absent bodies' rows are zeros.  positions=False,
+        velocities=False is the force curve alone.  Not under "balls"."""
+        p = self._params(dt, restitution, friction, threshold)
+        nsteps, every = int(nsteps), int(every)
+        S = nsteps // every if every >= 1 and nsteps >= 0 else 0
+        q = np.zeros((S, self.n_envs, self.n_bodies, 7)) if positions else None
+        v = np.zeros((S, self.n_envs, self.n_bodies, 6)) if velocities else None
+        net = np.zeros((S, self.n_envs, self.n_bodies, 6))
+        nf = C.c_int64()
+        _lib.check(self._L.rb_batch_run_sampled_impulses(self._h, nsteps, every, *p, _lib.ptr(q), _lib.ptr(v),
+                                                         _lib.ptr(net), C.byref(nf)), "rb_batch_run_sampled_impulses")
+        return q, v, net, nf.value
+
     def status(self):
         """(code (E,) int32: 0 or RB_EDOM (-33); steps_done (E,) int64)."""
         code = np.zeros(self.n_envs, np.int32)
@@ -531,6 +556,41 @@ class BatchWorld:
         _lib.check(self._L.rb_batch_run_sampled_dev(self._h, nsteps, every, *p, qp, vp, _IO_CODES[ts]),
                    "rb_batch_run_sampled_dev")
         return q, v
+
+    def run_sampled_impulses_device(self, nsteps: int, every: int, positions: bool = True, velocities: bool = True,
+                                    out_qpos=None, out_qvel=None, out_net=None, dtype=None, dt=None, restitution=None,
+                                    friction=None, threshold=None):
+        """run_sampled_impulses() with the samples in device memory: returns
+        (qpos (S, E, M, 7) or None, qvel (S, E, M, 6) or None, net (S, E, M,
+        6)), written into out_qpos / out_qvel / out_net or new torch tensors of
+        `dtype`, without waiting (sync() reports the failed environments)."""
+        p = self._params(dt, restitution, friction, threshold)
+        nsteps, every = int(nsteps), int(every)
+        S = nsteps // every if every >= 1 and nsteps >= 0 else 0
+        E, M = self.n_envs, self.n_bodies
+        if not positions and out_qpos is not None:
+            raise ValueError("out_qpos: given with positions=False")
+        if not velocities and out_qvel is not None:
+            raise ValueError("out_qvel: given with velocities=False")
+        names = ("out_qpos", "out_qvel", "out_net")
+        ts = _pair_typestr(self.dtype, names, (out_qpos, out_qvel, out_net), dtype)
+        shapes = ((S, E, M, 7), (S, E, M, 6), (S, E, M, 6))
+        want = (positions, velocities, True)
+        # the arrays that were given are checked before any is allocated
+        arrays = [a if w else None for a, w in zip((out_qpos, out_qvel, out_net), want)]
+        for name, a, shape in zip(names, arrays, shapes):
+            if a is not None:
+                _device_array(name, a, shape, (ts,), out=True)
+        arrays = [_new_tensor(shape, ts, self.device) if w and a is None else a
+                  for a, w, shape in zip(arrays, want, shapes)]
+        ptrs = [None if a is None else _device_array(name, a, shape, (ts,), out=True)[0]
+                for name, a, shape in zip(names, arrays, shapes)]
+        for name, a, ptr in zip(names, arrays, ptrs):
+            if S > 0 and a is not None and ptr is None:
+                raise ValueError(f"{name}: null device pointer")
+        _lib.check(self._L.rb_batch_run_sampled_impulses_dev(self._h, nsteps, every, *p, *ptrs, _IO_CODES[ts]),
+                   "rb_batch_run_sampled_impulses_dev")
+        return tuple(arrays)
 
     def contacts_device(self, max_records=None, geometry=True, dtype=None, out=None) -> BatchContacts:
         """contacts() of all environments into device memory, enqueued on the

@@ -71,6 +71,15 @@ geometry) of the same batch, alternating; seconds per call.  With --box-pile
 NX,NY,LAYERS the scene is that pile (the box instances of the query's
 kernel).  Writes to profiles/batch_impulses/ unless --out is given.
 
+--sampled-impulses EVERY: instead, the contact-impulse curves of a sampled run:
+run_sampled_impulses_device(steps, EVERY) with all three outputs and with net
+alone against run_sampled_device(steps, EVERY) of the same run, alternating,
+device tensors allocated once, one sync() per run (seconds per run; the ratios
+are what sensing costs inside the step loop).  With EVERY 1 also the loop the
+call replaces: impulses_device(max_records=0) + step_async(1) per step.  The
+environments run a friction sweep (0.2 .. 0.8); --box-pile selects the scene.
+Writes profiles/batch_sampled_impulses/sensed_<scene>_every<EVERY>.json.
+
 --ragged LO,HI: instead, an ensemble of E scenes whose body counts are spread
 evenly over LO..HI (--ragged-scene flat_spheres: rows of spheres; box_pile:
 columns of two cubes, the first n bodies), f64.  Three measurements in one
@@ -441,6 +450,75 @@ def bench_impulses(rb, sc, E, R, settle, reps, dtype, calls=20):
     return res
 
 
+def bench_sampled_impulses(rb, sc, E, steps, every, reps, dtype):
+    """Seconds per run, from the same start state, alternating, all through
+    device tensors allocated once and one sync() per run:
+    run_sampled_impulses_device(steps, every) with all three outputs and with
+    net alone, against run_sampled_device(steps, every) of the same run (what
+    sensing costs inside the loop); with every == 1 also the loop it replaces,
+    impulses_device(max_records=0) + step_async(1) per step.  The friction of
+    the environments is spread over 0.2 .. 0.8.  The net rows of the call and
+    of the loop must be the same words."""
+    import torch
+    q = np.broadcast_to(sc.qpos0, (E, sc.n, 7)).copy()
+    v = np.broadcast_to(sc.qvel0, (E, sc.n, 6)).copy()
+    S = steps // every
+    with rb.BatchWorld(sc, E, dtype=dtype) as b:
+        b.set_params(friction=np.linspace(0.2, 0.8, E))
+        b.use_stream(torch.cuda.current_stream().cuda_stream)
+        dev = f"cuda:{b.device}"
+        out_q = torch.empty((S, E, sc.n, 7), dtype=torch.float64, device=dev)
+        out_v = torch.empty((S, E, sc.n, 6), dtype=torch.float64, device=dev)
+        out_n = torch.empty((S, E, sc.n, 6), dtype=torch.float64, device=dev)
+        loop_n = torch.empty((S, E, sc.n, 6), dtype=torch.float64, device=dev) if every == 1 else None
+        counts = torch.empty((E, sc.n), dtype=torch.int32, device=dev)
+
+        def full():
+            b.run_sampled_impulses_device(steps, every, out_qpos=out_q, out_qvel=out_v, out_net=out_n)
+
+        def net_only():
+            b.run_sampled_impulses_device(steps, every, positions=False, velocities=False, out_net=out_n)
+
+        def plain():
+            b.run_sampled_device(steps, every, out_qpos=out_q, out_qvel=out_v)
+
+        def loop():
+            for s in range(steps):
+                b.impulses_device(max_records=0, out=dict(counts=counts, net=loop_n[s]))
+                b.step_async(1)
+
+        runs = dict(sensed_all=full, sensed_net_only=net_only, run_sampled_device=plain)
+        if every == 1:
+            runs["impulses_step_loop"] = loop
+        t = {k: [] for k in runs}
+        words = {}
+        for k, f in runs.items():                       # warm-up of each, and the comparison
+            b.set_state(q, v)
+            f()
+            failed = b.sync()
+            if k != "run_sampled_device":
+                words[k] = (loop_n if k == "impulses_step_loop" else out_n).cpu().numpy().view(np.uint64).copy()
+        same = all(np.array_equal(w, words["sensed_all"]) for w in words.values())
+        nonzero = int((words["sensed_all"] & 0x7fffffffffffffff != 0).any(axis=-1).sum())
+        del words
+        for _ in range(reps):
+            for k, f in runs.items():
+                b.set_state(q, v)
+                t0 = time.perf_counter()
+                f()
+                b.sync()
+                t[k].append(time.perf_counter() - t0)
+    res = dict(samples=S, every=every, failed=failed, net_identical=bool(same), nonzero_net_rows=nonzero,
+               **{k: _summary(x) for k, x in t.items()})
+    base = res["run_sampled_device"]["median"]
+    res["sensed_all_over_run_sampled"] = res["sensed_all"]["median"] / base
+    res["sensed_net_only_over_run_sampled"] = res["sensed_net_only"]["median"] / base
+    if every == 1:
+        res["loop_over_sensed_net_only"] = res["impulses_step_loop"]["median"] / res["sensed_net_only"]["median"]
+        res["loop_over_sensed_all"] = res["impulses_step_loop"]["median"] / res["sensed_all"]["median"]
+    return res
+
+
 def ragged_scene(variant, n, seed):
     """A scene of n bodies: a row of spheres, or the first n bodies of columns of two cubes."""
     from rbhip import scenes
@@ -547,6 +625,9 @@ def main():
                     help="time the contact query with R records per body, after --steps settling steps")
     ap.add_argument("--impulses", type=int, default=-1, metavar="R",
                     help="time the impulse query with R records per body, after --steps settling steps")
+    ap.add_argument("--sampled-impulses", type=int, default=0, metavar="EVERY",
+                    help="time run_sampled_impulses_device(steps, EVERY), all outputs and net alone, against "
+                         "run_sampled_device and, at EVERY 1, against impulses_device + step_async per step")
     ap.add_argument("--ragged", default="", metavar="LO,HI",
                     help="an ensemble with body counts spread over LO..HI: one ragged batch against one batch per shape")
     ap.add_argument("--ragged-scene", default="flat_spheres", choices=["flat_spheres", "box_pile"])
@@ -558,6 +639,9 @@ def main():
         if a.impulses >= 0:
             scene = "box_pile_" + a.box_pile.replace(",", "_") if a.box_pile else "multi_sphere4"
             a.out = os.path.join(ROOT, "profiles", "batch_impulses", f"impulses_{scene}_R{a.impulses}.json")
+        if a.sampled_impulses:
+            scene = "box_pile_" + a.box_pile.replace(",", "_") if a.box_pile else "multi_sphere4"
+            a.out = os.path.join(ROOT, "profiles", "batch_sampled_impulses", f"sensed_{scene}_every{a.sampled_impulses}.json")
 
     import rbhip
     from rbhip import scenes
@@ -577,6 +661,17 @@ def main():
             raise SystemExit("--ragged LO,HI: 1 <= LO <= HI <= 256")
         res.update(scene=f"ragged {a.ragged_scene}", bodies_per_env=hi, counts=f"{lo}..{hi}")
         res["ragged"] = {str(E): bench_ragged(rbhip, a.ragged_scene, lo, hi, E, a.steps, a.reps) for E in a.envs}
+    elif a.sampled_impulses:
+        if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or a.sampled_device or \
+                a.contacts >= 0 or a.impulses >= 0 or a.wide_pile or a.sampled_impulses < 1:
+            raise SystemExit("--sampled-impulses EVERY >= 1: on its own (with --box-pile for a mixed template), under the "
+                             "default law")
+        if a.box_pile:
+            sc = scenes.box_pile(*(int(t) for t in a.box_pile.split(",")))
+            res.update(scene=sc.name, bodies_per_env=sc.n)
+        res.update(unit="seconds per run", every=a.sampled_impulses)
+        res["sampled_impulses"] = {str(E): bench_sampled_impulses(rbhip, sc, E, a.steps, a.sampled_impulses, a.reps, a.dtype)
+                                   for E in a.envs}
     elif a.impulses >= 0:
         if a.law != "mujoco" or a.sampled or a.per_env or a.incline_sweep or a.device_loop or a.sampled_device or \
                 a.contacts >= 0 or a.wide_pile:
